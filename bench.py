@@ -2,7 +2,7 @@
 """
 bench.py -- real-time factor of the mask-based MVDR hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -15,18 +15,25 @@ covariance -> MVDR solve -> beamform -> iSTFT -> renorm) over the rank's shard,
 inputs resident in HBM as float32 C x N when the timed region starts.  Utterances
 shard independently: RCCL carries only the barriers and the max-over-ranks reduction.
 
-What the default command runs besides the K timed steps (N = 1, rank 0):
+The plain command sets up the shard, warms up, times the K steps and prints the line: the
+headline, `stage_ms` and the HBM `roofline` of stage 1, all from the HIP events of the timed
+steps themselves.  `--dump-outputs DIR` writes what the last timed step computed (rank 0's
+shard; see dump_outputs()) before the line is printed.
+
+What `--full` adds after the K timed steps (N = 1, rank 0):
   int16_ingest  the same shard resident as the wave files' interleaved 16-bit frames
                 (what every CLI user starts from); its step time is the headline's
                 sibling `pcm16_from_frames_*`
-  roofline      HIP-event kernel times of the timed steps + ONE profiled child
+  steady_state  200 more steps once the clocks have settled
+  roofline      the counters of ONE profiled child beside the HIP-event kernel times
                 (rocprofv3 --pmc, three counter passes over float32 and PCM16 steps)
   cpu_baseline  the numpy oracle on one host core over a bounded sample, and the
                 parity check of every distinct utterance of the timed shard
   full_batch    all 1000 utterances of configs[2] on the one GPU
   end_to_end    192 files, disk -> wav through the drop-in CLI (process wall clock)
 Everything else (sustained stepping, power, issue rates, the other BASELINE configs, the
-all-core CPU leg, the three-repeat end-to-end marginal rate) is `--aux 1`: tools/bench_aux.py.
+all-core CPU leg, the three-repeat end-to-end marginal rate) is `--aux 1` (implies `--full`):
+tools/bench_aux.py.
 
 The scalars a reader needs first are flat, at the top level AND inside `roofline` (the
 driver's record keeps the scalars of the contract's objects and only the names of the rest).
@@ -75,26 +82,49 @@ def parse():
     ap.add_argument("--beamformer", default="mvdr", choices=["mvdr", "gevd", "pmwf-0"])
     ap.add_argument("--distinct", type=int, default=16,
                     help="distinct synthetic utterances generated per rank (others are copies)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy "
+                         "(rank 0's shard, float32 / float64, under 64 MB: see dump_outputs())")
+    ap.add_argument("--full", action="store_true",
+                    help="N=1 only: after the headline, also run every other leg (steady state, int16 "
+                         "ingest, full batch, counters, CPU baseline and oracle parity, end to end); "
+                         "the options below marked --full tune them")
     ap.add_argument("--cpu-sample", type=int, default=64,
-                    help="utterances timed on the CPU oracle (0 = skip)")
+                    help="--full: utterances timed on the CPU oracle (0 = skip)")
     ap.add_argument("--full-batch", type=int, default=1000,
-                    help="N=1 only: also time the whole configs[2] batch of this many utterances on the "
+                    help="--full: also time the whole configs[2] batch of this many utterances on the "
                          "one GPU (strong-scaling anchor; 0 = skip)")
     ap.add_argument("--e2e-utts", type=int, default=192,
-                    help="N=1 only: files of the end-to-end CLI leg (0 = skip); --aux 1 adds 16 x as many, "
+                    help="--full: files of the end-to-end CLI leg (0 = skip); --aux 1 adds 16 x as many, "
                          "three repeats each")
     ap.add_argument("--pmc", type=int, default=1,
-                    help="N=1 only: HBM traffic and VALU instruction counts of the streaming kernels IN "
+                    help="--full: HBM traffic and VALU instruction counts of the streaming kernels IN "
                          "THIS RUN: a few steps re-run as a child under `rocprofv3 --pmc` (counters only, "
                          "one pass per counter group; 0 = skip)")
     ap.add_argument("--child", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--int16-ingest", type=int, default=1,
-                    help="N=1 only: the same shard fed as 16-bit PCM frames (0 = skip)")
-    ap.add_argument("--aux", type=int, default=0, help="N=1 only: the auxiliary legs (tools/bench_aux.py)")
+                    help="--full: the same shard fed as 16-bit PCM frames (0 = skip)")
+    ap.add_argument("--aux", type=int, default=0,
+                    help="N=1 only: the auxiliary legs (tools/bench_aux.py); implies --full")
     ap.add_argument("--sustain-sec", type=float, default=3.0, help="--aux: seconds of sustained stepping")
     ap.add_argument("--cpu-allcore-per-proc", type=int, default=3, help="--aux: utterances per CPU worker")
     ap.add_argument("--other-configs", type=int, default=1, help="--aux: BASELINE configs[1], [3], [4]")
-    return ap.parse_args()
+    args = ap.parse_args()
+    args.full = args.full or bool(args.aux)
+    return args
+
+
+def library_is_stale(build):
+    """Whether libsetk_hip.so is missing or older than a HIP source or header -- checked by
+    reading modification times only.  build_library() takes a lock file inside the tree even
+    when it has nothing to do, and the benchmark may run where build() left the tree
+    read-only: it is called only when there is something to build."""
+    deps = [os.path.join(build.CSRC, s) for s in build.SOURCES] + \
+           [os.path.normpath(os.path.join(build.CSRC, h)) for h in build.HEADERS]
+    if not os.path.exists(build.LIB):
+        return True
+    t = os.path.getmtime(build.LIB)
+    return any(os.path.getmtime(d) > t for d in deps)
 
 
 def free_port():
@@ -136,7 +166,8 @@ def main():
     import torch
     import torch.distributed as dist
     from setk_amd import build as _build
-    _build.build_library(force=False)  # no-op when the in-tree library is current
+    if library_is_stale(_build):
+        _build.build_library(force=False)
     from setk_amd import _ffi, synth
 
     if not torch.cuda.is_available():
@@ -254,7 +285,10 @@ def main():
             },
             "stage_ms": stage_dict(stage_ms),
         }
-    if rank == 0 and world == 1:
+        if args.dump_outputs:
+            # before any --full leg: those run the same buffers again, some on other inputs
+            dump_outputs(args.dump_outputs, torch, waves)
+    if rank == 0 and world == 1 and args.full:
         single_gpu_legs(args, out, ctx, _ffi, torch, synth, opts, step, audio, masks, waves,
                         C, N, T, L, U, nd, stage_ms, ms_per_step, b_k1, b_k2)
         out["bench_wall_s"] = round(time.perf_counter() - t_start, 1)
@@ -267,6 +301,30 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_BYTES = 60 * 10**6    # --dump-outputs writes less than this in all
+
+
+def dump_outputs(out_dir, torch, waves):
+    """--dump-outputs: the enhanced waveforms of the last timed step, i.e. what a caller of
+    setk_enhance_batch receives, as npy files:
+      waves.npy            [U, S]  every utterance of the shard at S sample positions
+      wave_positions.npy   [S]     those positions (float64, exact integers)
+    S = L (the whole output) when U x L float32 fits the budget; otherwise S positions drawn
+    without replacement by default_rng(0) and sorted -- the same set in every run with the same
+    arguments, so two builds compare output for output."""
+    U, L = len(waves), waves[0].numel()
+    S = min(L, (DUMP_BYTES - 4096) // (4 * U + 8))
+    if S < L:
+        pos = np.sort(np.random.default_rng(0).choice(L, size=S, replace=False))
+    else:
+        pos = np.arange(L)
+    idx = torch.from_numpy(pos).to(waves[0].device)
+    sample = torch.stack([w.index_select(0, idx) for w in waves]).cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "waves.npy"), sample.astype(np.float32, copy=False))
+    np.save(os.path.join(out_dir, "wave_positions.npy"), pos.astype(np.float64))
 
 
 def single_gpu_legs(args, out, ctx, _ffi, torch, synth, opts, step, audio, masks, waves,

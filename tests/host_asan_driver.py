@@ -20,6 +20,12 @@ from setk_amd import _ffi  # noqa: E402
 
 lib = _ffi.load_library()
 assert hasattr(lib, "hoststub_report"), "not the host-stub build: set SETK_LIB"
+# the stand-in must be the only HIP in this process (tests/test_host_asan.py runs it torch-free):
+# beside a real runtime -- torch's, loaded into the global scope -- the library's HIP calls would
+# reach a device under the sanitizer.  Checked before the first call.
+with open("/proc/self/maps") as _maps:
+    _real = sorted({ln.split()[-1] for ln in _maps if "libamdhip64" in ln or "libhsa-runtime" in ln})
+assert not _real, f"a real HIP runtime is loaded beside the stand-in: {_real}"
 lib.hipMalloc.argtypes = [ctypes.POINTER(c_void_p), c_size_t]
 lib.hipFree.argtypes = [c_void_p]
 lib.hipMemcpy.argtypes = [c_void_p, c_void_p, c_size_t, c_int]

@@ -45,9 +45,9 @@ def test_smoke_entry():
 
 
 def test_bench_contract_single_rank():
-    """bench.py prints ONE JSON line with the contract's fields, the roofline and cpu_baseline
+    """bench.py --full prints ONE JSON line with the contract's fields, the roofline and cpu_baseline
     objects, and the flat scalars of the record."""
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--e2e-utts", "6", "--cpu-sample", "2"] + SMALL,
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--full", "--e2e-utts", "6", "--cpu-sample", "2"] + SMALL,
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
     one = _json_line(r)
     for k in CONTRACT_KEYS:
@@ -99,8 +99,8 @@ def test_bench_contract_single_rank():
 
 
 def test_bench_contract_aux_legs():
-    """`--aux 1` (tools/bench_aux.py): the same line with the auxiliary legs added."""
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--aux", "1", "--e2e-utts", "6", "--cpu-sample", "1",
+    """`--full --aux 1` (tools/bench_aux.py): the same line with the auxiliary legs added."""
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--full", "--aux", "1", "--e2e-utts", "6", "--cpu-sample", "1",
                         "--cpu-allcore-per-proc", "0", "--other-configs", "0", "--sustain-sec", "0.2", "--pmc", "0"]
                        + SMALL, capture_output=True, text=True, timeout=900, cwd=ROOT)
     one = _json_line(r)
@@ -115,6 +115,38 @@ def test_bench_contract_aux_legs():
     assert "marginal_GBps_in" in e2e and "marginal_ms_per_utt" in e2e
     assert e2e["host_copy_GBps"]["1"] > 0
     assert one["roofline"]["pmc"] is None and one["roofline"]["traffic"] is None   # --pmc 0
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """Without --full the line holds the headline and what the timed steps measured, and no other
+    leg; --dump-outputs writes the last timed step's waveforms, which match the oracle."""
+    import numpy as np
+    from oracle import np_oracle as o
+    out_dir = tmp_path / "out"
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--dump-outputs", str(out_dir)] + SMALL,
+                       capture_output=True, text=True, timeout=900, cwd=ROOT)
+    one = _json_line(r)
+    for k in CONTRACT_KEYS:
+        assert k in one, k
+    assert one["n_gpus"] == 1 and one["steps"] == 2 and one["warmup"] == 1
+    audio = 6 * 4.0 * 2
+    assert abs(one["value"] * one["ms_per_step"] * 2 / 1e3 - audio) / audio < 1e-3
+    for k in ("cpu_baseline", "full_batch", "end_to_end", "int16_ingest", "other_configs",
+              "steady_state_ms_per_step", "pcm16_from_frames_ms_per_step"):
+        assert k not in one, k
+    assert one["roofline"]["pmc"] is None and one["roofline"]["kernel_ms"] > 0
+    assert sorted(os.listdir(out_dir)) == ["wave_positions.npy", "waves.npy"]
+    waves = np.load(out_dir / "waves.npy")
+    pos = np.load(out_dir / "wave_positions.npy")
+    assert waves.dtype == np.float32 and pos.dtype == np.float64
+    # 6 x 4 s fits the budget whole: every sample of every utterance
+    assert waves.shape == (6, pos.size) and np.array_equal(pos, np.arange(pos.size))
+    for i in (0, 5):
+        mix, sp, nz = o.synth_utterance(i, 8, 64000, return_parts=True)
+        ref = o.enhance_utterance(mix, o.irm_mask(sp, nz), kind="mvdr", gauge=True)
+        assert ref.shape == (pos.size,)
+        err = float(np.sqrt(np.mean((waves[i] - ref)**2)) / np.sqrt(np.mean(ref**2)))
+        assert err < 1e-3, (i, err)
 
 
 def test_bench_contract_two_ranks():

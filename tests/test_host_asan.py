@@ -41,8 +41,9 @@ def asan_env():
 
 
 def _drive(env, *args):
+    # torch-free: importing torch would put its HIP runtime beside the stand-in (the driver refuses)
     return subprocess.run([sys.executable, os.path.join(ROOT, "tests", "host_asan_driver.py"), *args],
-                          capture_output=True, text=True, env=env, timeout=900)
+                          capture_output=True, text=True, env=dict(env, SETK_TORCH_FREE="1"), timeout=900)
 
 
 def test_stand_in_is_refused_unless_asked_for(asan_env):

@@ -328,13 +328,14 @@ def test_kaldi_writer_roundtrip(tmp_path):
         assert np.array_equal(rd[k], m)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="reference tree not present")
 def test_kaldi_doc_archive_matches_reference_reader():
-    """doc/format_transform/asset/egs.ark (too large to commit) through both readers."""
+    """doc/format_transform/asset/egs.ark through both readers: its first two records, byte for
+    byte (tests/golden/doc_egs_head.ark; the whole archive is too large to commit), against what
+    the reference's reader decoded from them (ref_kaldi.npz)."""
     from setk_amd.libs.data_handler import ArchiveReader
     g = load_golden("ref_kaldi.npz")
-    got = list(ArchiveReader("/root/reference/doc/format_transform/asset/egs.ark"))
-    assert [k for k, _ in got] == list(g["doc_ark.keys"])
+    got = list(ArchiveReader(os.path.join(GOLDEN, "doc_egs_head.ark")))
+    assert [k for k, _ in got] == list(g["doc_ark.keys"][:2])
     for (k, m), shape, s, v in zip(got, g["doc_ark.shape"], g["doc_ark.sum"], g["doc_ark.m35"]):
         assert m.shape == tuple(shape)
         assert abs(float(np.sum(m, dtype=np.float64)) - s) < 1e-6 * abs(s)
@@ -406,11 +407,11 @@ def test_cli_surface_matches_reference():
         build_parser().parse_args(["--beamformer", "nope", "w", "m", "o"])
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="reference tree not present")
 def test_cli_options_equal_reference_parser():
-    """Every option string / default of the reference CLI exists here."""
-    src = open("/root/reference/scripts/sptk/apply_adaptive_beamformer.py").read()
-    ref_flags = set(re.findall(r'add_argument\("(--[a-z0-9.\-]+)"', src))
+    """Every option string of the reference CLI exists here (the reference's option strings:
+    tests/golden/ref_live.npz, oracle/make_golden.py gen_live)."""
+    ref_flags = set(str(f) for f in load_golden("ref_live.npz")["cli.adaptive_beamformer.options"])
+    assert len(ref_flags) >= 12 and all(f.startswith("--") for f in ref_flags)
     from setk_amd.sptk.apply_adaptive_beamformer import build_parser
     ours = set()
     for act in build_parser()._actions:
@@ -871,3 +872,56 @@ def test_shard_without_torch(tmp_path, world):
         assert o_["world"] == world and not o_["torch"] and o_["backend"] in ("rccl", "tcp")
         assert o_["tot"] == [37.0, float(total)] and o_["mx"] == [float(world - 1), 3.5]
     assert len({o_["backend"] for o_ in outs}) == 1
+
+
+def test_bench_dump_outputs_sample_is_fixed_and_under_64_mb(tmp_path):
+    """bench.py --dump-outputs at the default shard (125 x 30 s outputs, 240 MB whole): a seeded
+    sample of positions, the same in every run, and under 64 MB on disk (host tensors stand in for
+    the device buffers)."""
+    import importlib.util
+    import torch
+    spec = importlib.util.spec_from_file_location("setk_bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    L = 480000
+    base = torch.arange(L, dtype=torch.float32)
+    waves = [base + i for i in range(125)]
+    sizes = []
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), torch, waves)
+        sizes.append(sum(os.path.getsize(tmp_path / run / f) for f in os.listdir(tmp_path / run)))
+    a, pa = np.load(tmp_path / "a" / "waves.npy"), np.load(tmp_path / "a" / "wave_positions.npy")
+    pb = np.load(tmp_path / "b" / "wave_positions.npy")
+    assert a.dtype == np.float32 and pa.dtype == np.float64 and np.array_equal(pa, pb)
+    assert max(sizes) < 64 * 10**6 and a.shape == (125, pa.size) and pa.size > 100000
+    assert np.all(np.diff(pa) > 0) and pa[-1] < L
+    assert np.array_equal(a, pa[None, :].astype(np.float32) + np.arange(125, dtype=np.float32)[:, None])
+
+
+def test_bench_checks_the_library_without_writing_to_the_tree(tmp_path):
+    """bench.py calls the builder only when libsetk_hip.so is missing or older than a source or
+    header, and decides that from modification times alone (it may run on a read-only tree)."""
+    import importlib.util
+    import types
+    spec = importlib.util.spec_from_file_location("setk_bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    csrc = tmp_path / "csrc"
+    csrc.mkdir()
+    (tmp_path / "include").mkdir()
+    b = types.SimpleNamespace(CSRC=str(csrc), SOURCES=["a.hip"], HEADERS=["c.h", "../include/h.h"],
+                              LIB=str(tmp_path / "lib.so"))
+    for p in (csrc / "a.hip", csrc / "c.h", tmp_path / "include" / "h.h"):
+        p.write_text("x")
+        os.utime(p, (1000, 1000))
+    assert bench.library_is_stale(b)                 # no library
+    (tmp_path / "lib.so").write_text("x")
+    os.utime(tmp_path / "lib.so", (2000, 2000))
+    before = sorted(os.listdir(tmp_path)) + sorted(os.listdir(csrc))
+    assert not bench.library_is_stale(b)
+    assert sorted(os.listdir(tmp_path)) + sorted(os.listdir(csrc)) == before
+    os.utime(tmp_path / "include" / "h.h", (3000, 3000))
+    assert bench.library_is_stale(b)                 # a header newer than the library
+    os.utime(tmp_path / "include" / "h.h", (1000, 1000))
+    os.utime(csrc / "a.hip", (3000, 3000))
+    assert bench.library_is_stale(b)                 # a source newer than the library

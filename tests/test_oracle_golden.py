@@ -3,7 +3,8 @@ Pins the CPU oracle (oracle/np_oracle.py) against
   (i)  the reference's stored doc vectors (doc/adaptive_beamformer/asset),
   (ii) vectors produced by the unmodified reference modules
        (oracle/make_golden.py -> tests/golden/*.npz),
-  (iii) the live reference, when /root/reference is present.
+  (iii) what the live reference answered on seeded cases, recorded once
+       (oracle/make_golden.py gen_live -> tests/golden/ref_live.npz).
 """
 import os
 
@@ -13,7 +14,6 @@ import pytest
 from conftest import load_golden, pcm16_rel_rms, rms, rel_rms
 from oracle import np_oracle as o
 from oracle import make_golden as mg
-from oracle import ref_harness as rh
 
 STFT_KW = dict(frame_len=512, frame_hop=256, window="hann", center=True)
 
@@ -37,6 +37,11 @@ def per_bin_gain_fit(ours, stored):
     energy = np.sum(np.abs(B)**2, axis=1)
     g = np.where(energy > 1e-4 * np.max(energy), g, np.median(np.abs(g)))
     return g, rms(g[:, None] * A, B) / max(rms(B), 1e-30)
+
+
+@pytest.fixture(scope="module")
+def live():
+    return load_golden("ref_live.npz")
 
 
 @pytest.fixture(scope="module")
@@ -201,18 +206,21 @@ def test_cli_goldens():
             assert err < 2e-3, (i, bf, err)
 
 
-@pytest.mark.skipif(not rh.available(), reason="reference tree not present")
-def test_live_reference_enhance():
-    """Oracle == live reference on a fresh seeded case (incl. VAD + post-mask)."""
-    libs = rh.load()
+def test_live_reference_enhance(live):
+    """Oracle == live reference on a fresh seeded case (incl. VAD + post-mask): the reference's
+    MVDR output of that case as it recorded it (ref_live.npz), fed the oracle's STFT, which
+    equals the reference's on a seeded sample of the spectrogram's bins."""
     mix, sp, nz = o.synth_utterance(42, 6, 7000, return_parts=True)
     mask = o.irm_mask(sp, nz)
     kw = dict(frame_len=512, frame_hop=256, window="hann", center=True,
               transpose=False)
-    obs = np.stack([libs.utils.forward_stft(s, round_power_of_two=True, **kw)
-                    for s in mix])
-    ref = libs.beamformer.MvdrBeamformer(257).run(mask, obs)
+    obs = np.stack([o.forward_stft(s, round_power_of_two=True, **kw) for s in mix])
+    idx = live["mvdr.obs_index"]
+    assert np.array_equal(idx, mg.live_obs_index(obs.shape))
+    assert rel_rms(obs.reshape(-1)[idx], live["mvdr.obs_sample"]) < 1e-6
+    ref = live["mvdr.enh"]
     ours = o.supervised_run("mvdr", mask, obs)
+    assert ours.shape == ref.shape
     assert rel_rms(ours, ref) < 1e-5
 
 
@@ -280,31 +288,27 @@ def test_wpe_doc_assets():
     assert best / rms(stored) < 1e-3, best / rms(stored)
 
 
-@pytest.mark.skipif(not rh.available(), reason="reference tree not present")
-def test_cgmm_update_alpha_equals_live_reference():
-    libs = rh.load()
+def test_cgmm_update_alpha_equals_live_reference(live):
     mix = o.synth_utterance(61, 4, 12000)
     obs = o.multichannel_stft(mix, transpose=False, **STFT_KW)
     for ua in (False, True):
-        ref = libs.cluster.CgmmTrainer(obs, 2, update_alpha=ua).train(5)
-        assert np.max(np.abs(o.cgmm_gamma(obs, 5, update_alpha=ua) - ref)) < 1e-9
+        ref = mg.with_last_class(live[f"cgmm2.update_alpha{int(ua)}"])
+        got = o.cgmm_gamma(obs, 5, update_alpha=ua)
+        assert got.shape == ref.shape and np.max(np.abs(got - ref)) < 1e-9
 
 
-@pytest.mark.skipif(not rh.available(), reason="reference tree not present")
-def test_cgmm_three_classes_seeded_start_equals_live_reference():
+def test_cgmm_three_classes_seeded_start_equals_live_reference(live):
     """num_classes != 2: the reference starts from np.random.uniform(size=[K, F, T]) of the legacy
     GLOBAL generator, which its CLI seeds with --seed (estimate_cgmm_masks.py:28, 95-98) -- a
     reproducible start (the round-3 text called it unseeded: wrong).  The oracle draws from the
     same generator in the same order: first utterance after the seed, then the second."""
-    libs = rh.load()
     obs1 = o.multichannel_stft(o.synth_utterance(62, 4, 9000), transpose=False, **STFT_KW)
     obs2 = o.multichannel_stft(o.synth_utterance(63, 4, 7000), transpose=False, **STFT_KW)
-    np.random.seed(777)
-    ref1 = libs.cluster.CgmmTrainer(obs1, 3).train(4)
-    ref2 = libs.cluster.CgmmTrainer(obs2, 3, update_alpha=True).train(4)
+    # after np.random.seed(777), in this order
+    ref1, ref2 = (mg.with_last_class(live[k]) for k in ("cgmm3.first", "cgmm3.second"))
     got1 = o.cgmm_gamma(obs1, 4, num_classes=3, seed=777)
     got2 = o.cgmm_gamma(obs2, 4, num_classes=3, update_alpha=True)  # generator state carried over
-    assert ref1.shape == got1.shape == (3,) + obs1.shape[1:]
+    assert ref1.shape == got1.shape == (3,) + obs1.shape[1:] and ref2.shape == got2.shape
     assert np.max(np.abs(got1 - ref1)) < 1e-9 and np.max(np.abs(got2 - ref2)) < 1e-9
 
 
@@ -436,17 +440,16 @@ def test_oracle_skip_set_equals_the_reference():
         assert table[name]["gevd"] != "LinAlgError"  # the GEV path never raises (:54-59)
 
 
-@pytest.mark.skipif(not rh.available(), reason="reference tree not present")
-def test_skip_set_table_equals_the_live_reference():
+def test_skip_set_table_equals_the_live_reference(live):
+    """The committed table against what the live reference answered on the same eight cases
+    (ref_live.npz), and those cases' inputs byte for byte the ones it was asked about."""
     import json
-    import warnings
     table = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "ref_skipset.json")))["table"]
-    libs = rh.load()
     cases = _skipset_inputs()
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        for name in ("plain", "dup-channel", "channel-x2", "channel-x0.3", "ones-mask", "silence",
-                     "real-noisy-5ch", "real-ssl-first-8ch"):
-            samps, mask = cases[name]
-            for kname, spec in o.SKIPSET_KINDS.items():
-                assert mg.ref_skipset_outcome(libs, samps, mask, spec) == table[name][kname], (name, kname)
+    names = [str(n) for n in live["skipset.names"]]
+    kinds = [str(k) for k in live["skipset.kinds"]]
+    assert names == list(mg.skipset_live_names()) and kinds == list(o.SKIPSET_KINDS)
+    for i, name in enumerate(names):
+        assert mg.skipset_input_sha256(*cases[name]) == live["skipset.input_sha256"][i], name
+        for j, kname in enumerate(kinds):
+            assert live["skipset.outcome"][i, j] == table[name][kname], (name, kname)

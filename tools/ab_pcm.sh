@@ -7,7 +7,7 @@ R=$1; shift
 for r in $(seq $R); do
   for L in "$@"; do
     if [ "$L" = default ]; then unset SETK_LIB; else export SETK_LIB=$PWD/$L; fi
-    python bench.py --steps 100 --warmup 30 --cpu-sample 0 --full-batch 0 --e2e-utts 0 2>/dev/null | tail -1 > /tmp/ab.json
+    python bench.py --full --steps 100 --warmup 30 --cpu-sample 0 --full-batch 0 --e2e-utts 0 2>/dev/null | tail -1 > /tmp/ab.json
     python - "$L" $r <<'PY'
 import json, sys
 d = json.load(open("/tmp/ab.json"))

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """
-The auxiliary legs of bench.py (`python bench.py --aux 1`, N = 1 only): everything that is not the
+The auxiliary legs of bench.py (`python bench.py --full --aux 1`, N = 1 only): everything that is not the
 contract's timed steps, their counters, the CPU baseline and the whole-batch anchor.  Kept apart so
 that the driver's command stays short; every leg reports into the same JSON line.
 

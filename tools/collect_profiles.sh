@@ -35,5 +35,5 @@ python bench.py $B --steps 20 --warmup 3 --beamformer gevd 2>/dev/null | tail -1
 python bench.py $B --steps 20 --warmup 3 --channels 4 --seconds 10 --utts 500 2>/dev/null | tail -1 > "$OUT/cfg1_mvdr4/bench_unprofiled.json"
 python tools/bench_cgmm.py --utts 125 --seconds 30 --steps 3 2>/dev/null | tail -1 > "$OUT/cfg4_cgmm6/bench_unprofiled.json"
 # the full default line (CPU legs, end-to-end leg)
-python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
 find "$OUT" -name "*kernel_stats.csv" | head; tail -c 1500 "$OUT/bench.json"

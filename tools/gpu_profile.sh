@@ -17,7 +17,7 @@ timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt3 -- $B
 cp $(find $O/kt3 -name "*kernel_stats.csv" | head -1) $O/cfg3_kernel_stats.csv
 rm -rf $O/kt1 $O/kt2 $O/kt3 $O/kt4
 head -8 $O/cfg2_kernel_stats.csv | cut -c1-200
-( time timeout 1500 python bench.py --aux 1 ) > $O/bench_aux.json 2> $O/bench_aux.err
+( time timeout 1500 python bench.py --full --aux 1 ) > $O/bench_aux.json 2> $O/bench_aux.err
 tail -4 $O/bench_aux.err
 python - <<PY
 import json

@@ -4,7 +4,7 @@ TAG=$1; OUT=gpurun_out/$TAG; mkdir -p "$OUT"; export TMPDIR=/tmp
 timeout 1200 python -m pytest $2 -m gpu -x -q -s > "$OUT/pytest.log" 2>&1
 echo "pytest rc=$?"; tail -25 "$OUT/pytest.log"
 if [ -n "$3" ]; then
-  timeout 900 python bench.py $3 > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?"
+  timeout 900 python bench.py --full $3 > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?"
   python - "$OUT/bench.json" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -8,7 +8,7 @@ if [ -n "$PYT" ]; then
   timeout 1500 python -m pytest $PYT -m gpu -x -q > "$OUT/pytest.log" 2>&1
   echo "pytest rc=$?"; tail -15 "$OUT/pytest.log"
 fi
-B="python bench.py --steps 20 --warmup 3 --cpu-sample 1 --cpu-allcore-per-proc 0 --e2e-utts 0 --full-batch 0 --sustain-sec 0 --other-configs 0 --pmc 0"
+B="python bench.py --full --steps 20 --warmup 3 --cpu-sample 1 --cpu-allcore-per-proc 0 --e2e-utts 0 --full-batch 0 --sustain-sec 0 --other-configs 0 --pmc 0"
 for rep in 1 2 3; do
   for spec in "$@"; do
     ENVS=$spec; [ "$spec" = "-" ] && ENVS=""

@@ -4,7 +4,7 @@
 #   bash tools/stall_pcm.sh   -> gpurun_out/round6_stall/stall_pcm.md
 export TMPDIR=/tmp
 O=gpurun_out/round6_stall; mkdir -p $O
-BENCH="python bench.py --steps 3 --warmup 1 --cpu-sample 0 --pmc 0 --full-batch 0 --e2e-utts 0"
+BENCH="python bench.py --full --steps 3 --warmup 1 --cpu-sample 0 --pmc 0 --full-batch 0 --e2e-utts 0"
 G1="SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU"
 G2="SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_MISC SQ_ACTIVE_INST_FLAT SQ_WAIT_INST_LDS SQ_INST_CYCLES_VMEM SQ_INSTS_LDS"
 G3="SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_SMEM SQ_INSTS_BRANCH GRBM_GUI_ACTIVE"
