@@ -38,10 +38,7 @@ constexpr int kCgInitId = 0, kCgInitMask = 1, kCgEm = 2;
 // frames per partial-sum chunk: one wavefront folds a chunk in float32, the chunks are summed in
 // float64 (cgmm_finalize).  Shorter chunks = more waves and more partial traffic
 // (configs[4], 125 x 30 s: 41.1 ms with 64, 39.5 with 128, 38.6 - 39.1 with 192).
-#ifndef SETK_CG_CHUNK
-#define SETK_CG_CHUNK 128
-#endif
-constexpr int kCgChunk = SETK_CG_CHUNK;
+constexpr int kCgChunk = 128;
 
 struct CgmmArgs {
     const cf* spec;          // [C][T][spitch], F entries used per row

@@ -192,14 +192,6 @@ ZD float sgpr(float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
 }
 
-// per-class parameters of the E-step, uniform over the workgroup
-template <int C>
-struct ClassPar {
-    static constexpr int NPO = C * (C - 1) / 2;
-    float lre[NPO > 0 ? NPO : 1], lim[NPO > 0 ? NPO : 1];  // L_ij, i > j, row-major lower
-    float rd[C];                                           // 1 / L_ii
-    float ld, alpha;
-};
 template <int C>
 struct ParLayout {
     static constexpr int NPO = C * (C - 1) / 2;
@@ -207,32 +199,15 @@ struct ParLayout {
                          SIZE = ((ALPHA + 1 + 3) / 4) * 4;
 };
 
-template <int C>
-ZD void load_par(const float* p, ClassPar<C>& cp) {
-    typedef ParLayout<C> PL;
-#pragma unroll
-    for (int e = 0; e < PL::NPO; ++e) {
-        cp.lre[e] = sgpr(p[PL::LRE + e]);
-        cp.lim[e] = sgpr(p[PL::LIM + e]);
-    }
-#pragma unroll
-    for (int i = 0; i < C; ++i) cp.rd[i] = sgpr(p[PL::RD + i]);
-    cp.ld = sgpr(p[PL::LD]);
-    cp.alpha = sgpr(p[PL::ALPHA]);
-}
-
 // ---- packed fp32 (v_pk_*_f32: one instruction on an aligned VGPR pair) -------------------------
-// SETK_CGMM_PK=1: the frames phases hold a complex sample as a pair (re, im) and the two classes'
-// accumulators of one outer-product entry as a pair (class 0, class 1).  A complex multiply-
-// accumulate of the forward substitution is two packed instructions where the plain form needs
-// four, x_i conj(x_j) two instead of four, the two classes' weighted sums of one entry ONE
-// instead of two; broadcasts, swaps and signs ride in op_sel / neg (inline assembly: the compiler
-// folds broadcasts but not the mixed negations; not volatile, so it schedules freely).  The waves
+// The frames phases hold a complex sample as a pair (re, im) and the two classes' accumulators
+// of one outer-product entry as a pair (class 0, class 1).  A complex multiply-accumulate of the
+// forward substitution is two packed instructions where the plain form needs four, x_i conj(x_j)
+// two instead of four, the two classes' weighted sums of one entry ONE instead of two;
+// broadcasts, swaps and signs ride in op_sel / neg (inline assembly: the compiler folds
+// broadcasts but not the mixed negations; not volatile, so it schedules freely).  The waves
 // of this kernel are issue-limited one by one (section 5 of DESIGN.md), which is where a packed
 // instruction pays: round 2 measured none at the occupancy of the streaming kernels.
-#ifndef SETK_CGMM_PK
-#define SETK_CGMM_PK 1
-#endif
 typedef float pk2 __attribute__((ext_vector_type(2)));
 // t - (l.x + i l.y) * y with a uniform l (an SGPR pair): the step of y = L^-1 x
 ZD pk2 pk_cmsub_s(pk2 t, pk2 l, pk2 y) {
@@ -274,7 +249,8 @@ ZD pk2 pk_scale_s_hi(pk2 t, pk2 s) {
     return r;
 }
 
-// the packed form of ClassPar: (L_ij.re, L_ij.im) and (1 / L_ii, 1 / L_i+1,i+1) as uniform pairs
+// per-class parameters of the E-step, uniform over the workgroup: (L_ij.re, L_ij.im), i > j,
+// row-major lower, and (1 / L_ii, 1 / L_i+1,i+1) as pairs
 template <int C>
 struct ClassParPk {
     static constexpr int NPO = C * (C - 1) / 2;
@@ -290,7 +266,7 @@ ZD void load_par_pk(const float* p, ClassParPk<C>& cp) {
     for (int i = 0; i < (C + 1) / 2; ++i)
         cp.rd[i] = (pk2){sgpr(p[PL::RD + 2 * i]), (2 * i + 1 < C) ? sgpr(p[PL::RD + 2 * i + 1]) : 0.f};
 }
-// q = | L^-1 x |^2, the operations of quad_form pair by pair
+// q = | L^-1 x |^2 by forward substitution, on pairs
 template <int C>
 ZD float quad_form_pk(const pk2 (&x)[C], const ClassParPk<C>& cp) {
     pk2 y[C];
@@ -304,65 +280,6 @@ ZD float quad_form_pk(const pk2 (&x)[C], const ClassParPk<C>& cp) {
         q2 = __builtin_elementwise_fma(y[i], y[i], q2);
     }
     return q2.x + q2.y;
-}
-
-// q = | L^-1 x |^2 by forward substitution
-template <int C>
-ZD float quad_form(const cf (&x)[C], const ClassPar<C>& cp) {
-    cf y[C];
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < C; ++i) {
-        float re = x[i].x, im = x[i].y;
-#pragma unroll
-        for (int j = 0; j < i; ++j) {
-            const int e = i * (i - 1) / 2 + j;
-            re = fmaf(-cp.lre[e], y[j].x, re);
-            re = fmaf(cp.lim[e], y[j].y, re);
-            im = fmaf(-cp.lre[e], y[j].y, im);
-            im = fmaf(-cp.lim[e], y[j].x, im);
-        }
-        y[i].x = re * cp.rd[i];
-        y[i].y = im * cp.rd[i];
-        q = fmaf(y[i].x, y[i].x, q);
-        q = fmaf(y[i].y, y[i].y, q);
-    }
-    return q;
-}
-
-template <int C>
-struct Acc {
-    static constexpr int NP = C * (C + 1) / 2, NPO = C * (C - 1) / 2;
-    float re[2][NP];
-    float im[2][NPO > 0 ? NPO : 1];
-    float sg[2];
-};
-
-// acc_k += w_k x x^H (upper triangle i <= j, entry x_i conj(x_j))
-template <int C, bool BOTH>
-ZD void accumulate(const cf (&x)[C], float w0, float w1, Acc<C>& a) {
-    int e = 0, eo = 0;
-#pragma unroll
-    for (int i = 0; i < C; ++i)
-#pragma unroll
-        for (int j = i; j < C; ++j) {
-            if (i == j) {
-                const float p = fmaf(x[i].x, x[i].x, x[i].y * x[i].y);
-                a.re[0][e] = fmaf(w0, p, a.re[0][e]);
-                if (BOTH) a.re[1][e] = fmaf(w1, p, a.re[1][e]);
-            } else {
-                const float pr = fmaf(x[i].x, x[j].x, x[i].y * x[j].y);
-                const float pi = fmaf(x[i].y, x[j].x, -x[i].x * x[j].y);
-                a.re[0][e] = fmaf(w0, pr, a.re[0][e]);
-                a.im[0][eo] = fmaf(w0, pi, a.im[0][eo]);
-                if (BOTH) {
-                    a.re[1][e] = fmaf(w1, pr, a.re[1][e]);
-                    a.im[1][eo] = fmaf(w1, pi, a.im[1][eo]);
-                }
-                ++eo;
-            }
-            ++e;
-        }
 }
 
 // circle-method partner of index k in round r of a sweep over m (even) indices
@@ -743,18 +660,7 @@ ZD void frames_pass(BinSmem<C, NT>& sm, const int tid, const int T, const cf (&x
                     const cf* Xs, const int Tlp, const CgmmBinArgs& a, const int f) {
     typedef BinSmem<C, NT> S;
     typedef ParLayout<C> PL;
-    constexpr int NP = S::NP, NPO = S::NPO, NV = S::NV;
-    auto getx = [&](auto uc, cf (&x)[C]) {
-        constexpr int u = decltype(uc)::value;
-        if constexpr (u < RF) {
-#pragma unroll
-            for (int c = 0; c < C; ++c) x[c] = xr[u][c];
-        } else {
-#pragma unroll
-            for (int c = 0; c < C; ++c) x[c] = Xs[c * Tlp + tid + NT * (u - RF)];
-        }
-    };
-    constexpr bool PK = SETK_CGMM_PK != 0;
+    constexpr int NP = S::NP, NV = S::NV;
     auto getxp = [&](auto uc, pk2 (&x)[C]) {
         constexpr int u = decltype(uc)::value;
 #pragma unroll
@@ -789,33 +695,18 @@ ZD void frames_pass(BinSmem<C, NT>& sm, const int tid, const int T, const cf (&x
     } else {
         float q0[U], q1[U];
         auto e_phase = [&](const float* par, float (&q)[U]) __attribute__((always_inline)) {
-            if constexpr (PK) {
-                ClassParPk<C> p;
-                load_par_pk<C>(par, p);
-                static_for<U>([&](auto uc) {
-                    constexpr int u = decltype(uc)::value;
-                    q[u] = 1.f;
-                    if (tid + NT * u < T) {
-                        pk2 x[C];
-                        getxp(uc, x);
-                        q[u] = quad_form_pk<C>(x, p);
-                    }
-                    reload_fence();
-                });
-            } else {
-                ClassPar<C> p;
-                load_par<C>(par, p);
-                static_for<U>([&](auto uc) {
-                    constexpr int u = decltype(uc)::value;
-                    q[u] = 1.f;
-                    if (tid + NT * u < T) {
-                        cf x[C];
-                        getx(uc, x);
-                        q[u] = quad_form<C>(x, p);
-                    }
-                    reload_fence();
-                });
-            }
+            ClassParPk<C> p;
+            load_par_pk<C>(par, p);
+            static_for<U>([&](auto uc) {
+                constexpr int u = decltype(uc)::value;
+                q[u] = 1.f;
+                if (tid + NT * u < T) {
+                    pk2 x[C];
+                    getxp(uc, x);
+                    q[u] = quad_form_pk<C>(x, p);
+                }
+                reload_fence();
+            });
         };
         e_phase(sm.par[0], q0);
         reload_fence();
@@ -859,180 +750,97 @@ ZD void frames_pass(BinSmem<C, NT>& sm, const int tid, const int T, const cf (&x
     const int wave = tid >> 6, lane = tid & 63;
     float* row = sm.red[wave];
     const bool wr = lane >= 60;
-    // ---- packed form: the entries (i <= j) in two row groups (as many registers as the plain
-    //      phases hold); per group ONE pass over the frames for both parts and both classes: an
-    //      entry's two class sums are a pair, x_i conj(x_j) gives real and imaginary part at once ----
-    if constexpr (PK) {
-        // rows [0, RS) hold at least half of the NP entries
-        constexpr int RS = [] {
-            int n = 0, r = 0;
-            while (r < C && 2 * n < NP) n += C - r++;
-            return r;
-        }();
-        auto group = [&](auto lo_c, auto hi_c, auto last_c) __attribute__((always_inline)) {
-            constexpr int ILO = decltype(lo_c)::value, IHI = decltype(hi_c)::value;
-            constexpr bool LAST = decltype(last_c)::value;
-            // entries of rows [ILO, IHI): e in [ELO, ELO + NR), off-diagonal eo in [OLO, OLO + NI)
-            constexpr int ELO = ILO * C - ILO * (ILO - 1) / 2, EHI = IHI * C - IHI * (IHI - 1) / 2;
-            constexpr int NR = EHI - ELO, NIo = NR - (IHI - ILO);
-            constexpr int OLO = ELO - ILO;
-            constexpr int NVAL = 2 * NR + 2 * NIo + (LAST ? 2 : 0);
-            if constexpr (NR > 0) {
-                pk2 accR[NR], accI[NIo > 0 ? NIo : 1];
+    // ---- the entries (i <= j) in two row groups; per group ONE pass over the frames for both
+    //      parts and both classes: an entry's two class sums are a pair, x_i conj(x_j) gives real
+    //      and imaginary part at once ----
+    // rows [0, RS) hold at least half of the NP entries
+    constexpr int RS = [] {
+        int n = 0, r = 0;
+        while (r < C && 2 * n < NP) n += C - r++;
+        return r;
+    }();
+    auto group = [&](auto lo_c, auto hi_c, auto last_c) __attribute__((always_inline)) {
+        constexpr int ILO = decltype(lo_c)::value, IHI = decltype(hi_c)::value;
+        constexpr bool LAST = decltype(last_c)::value;
+        // entries of rows [ILO, IHI): e in [ELO, ELO + NR), off-diagonal eo in [OLO, OLO + NI)
+        constexpr int ELO = ILO * C - ILO * (ILO - 1) / 2, EHI = IHI * C - IHI * (IHI - 1) / 2;
+        constexpr int NR = EHI - ELO, NIo = NR - (IHI - ILO);
+        constexpr int OLO = ELO - ILO;
+        constexpr int NVAL = 2 * NR + 2 * NIo + (LAST ? 2 : 0);
+        if constexpr (NR > 0) {
+            pk2 accR[NR], accI[NIo > 0 ? NIo : 1];
 #pragma unroll
-                for (int e = 0; e < NR; ++e) accR[e] = (pk2){0.f, 0.f};
+            for (int e = 0; e < NR; ++e) accR[e] = (pk2){0.f, 0.f};
 #pragma unroll
-                for (int e = 0; e < (NIo > 0 ? NIo : 1); ++e) accI[e] = (pk2){0.f, 0.f};
-                static_for<U>([&](auto uc) {
-                    constexpr int u = decltype(uc)::value;
-                    if (tid + NT * u < T) {
-                        pk2 x[C];
-                        getxp(uc, x);
-                        const pk2 w = (pk2){w0[u], w1[u]};
-                        int e = 0, eo = 0;
+            for (int e = 0; e < (NIo > 0 ? NIo : 1); ++e) accI[e] = (pk2){0.f, 0.f};
+            static_for<U>([&](auto uc) {
+                constexpr int u = decltype(uc)::value;
+                if (tid + NT * u < T) {
+                    pk2 x[C];
+                    getxp(uc, x);
+                    const pk2 w = (pk2){w0[u], w1[u]};
+                    int e = 0, eo = 0;
 #pragma unroll
-                        for (int i = ILO; i < IHI; ++i)
+                    for (int i = ILO; i < IHI; ++i)
 #pragma unroll
-                            for (int j = i; j < C; ++j) {
-                                if (i == j) {
-                                    const pk2 t2 = x[i] * x[i];
-                                    pk2 pp;
-                                    asm("v_pk_add_f32 %0, %1, %1 op_sel:[0,1] op_sel_hi:[1,0]" : "=v"(pp) : "v"(t2));
-                                    accR[e] = __builtin_elementwise_fma(pp, w, accR[e]);
-                                } else {
-                                    const pk2 pq = pk_cmulc(x[i], x[j]);
-                                    accR[e] = pk_fma_bc_lo(pq, w, accR[e]);
-                                    accI[eo] = pk_fma_bc_hi(pq, w, accI[eo]);
-                                    ++eo;
-                                }
-                                ++e;
+                        for (int j = i; j < C; ++j) {
+                            if (i == j) {
+                                const pk2 t2 = x[i] * x[i];
+                                pk2 pp;
+                                asm("v_pk_add_f32 %0, %1, %1 op_sel:[0,1] op_sel_hi:[1,0]" : "=v"(pp) : "v"(t2));
+                                accR[e] = __builtin_elementwise_fma(pp, w, accR[e]);
+                            } else {
+                                const pk2 pq = pk_cmulc(x[i], x[j]);
+                                accR[e] = pk_fma_bc_lo(pq, w, accR[e]);
+                                accI[eo] = pk_fma_bc_hi(pq, w, accI[eo]);
+                                ++eo;
                             }
-                    }
-                    reload_fence();
-                });
-                PH(tm, tid == 0, LAST ? 13 : 11);
-                // [re class 0 | re class 1 | im class 0 | im class 1 | the two posterior sums]
-                float v[NVAL];
-#pragma unroll
-                for (int e = 0; e < NR; ++e) {
-                    v[e] = accR[e].x;
-                    v[NR + e] = accR[e].y;
-                }
-#pragma unroll
-                for (int e = 0; e < NIo; ++e) {
-                    v[2 * NR + e] = accI[e].x;
-                    v[2 * NR + NIo + e] = accI[e].y;
-                }
-                if constexpr (LAST) {
-                    v[NVAL - 2] = sg0;
-                    v[NVAL - 1] = sg1;
-                }
-                float tot[Bfly<NVAL>::N2];
-                butterfly_sum<NVAL>(v, tot, lane);
-                if (wr) {
-#pragma unroll
-                    for (int r = 0; r < Bfly<NVAL>::N2; ++r) {
-                        const int i = butterfly_index<NVAL>(lane & 3, r);
-                        if (i >= 0) {
-                            int dst;
-                            if (i < NR) dst = ELO + i;
-                            else if (i < 2 * NR) dst = NV + ELO + (i - NR);
-                            else if (i < 2 * NR + NIo) dst = NP + OLO + (i - 2 * NR);
-                            else if (i < 2 * NR + 2 * NIo) dst = NV + NP + OLO + (i - 2 * NR - NIo);
-                            else dst = (i == NVAL - 2) ? NV - 1 : 2 * NV - 1;
-                            row[dst] = tot[r];
+                            ++e;
                         }
+                }
+                reload_fence();
+            });
+            PH(tm, tid == 0, LAST ? 13 : 11);
+            // [re class 0 | re class 1 | im class 0 | im class 1 | the two posterior sums]
+            float v[NVAL];
+#pragma unroll
+            for (int e = 0; e < NR; ++e) {
+                v[e] = accR[e].x;
+                v[NR + e] = accR[e].y;
+            }
+#pragma unroll
+            for (int e = 0; e < NIo; ++e) {
+                v[2 * NR + e] = accI[e].x;
+                v[2 * NR + NIo + e] = accI[e].y;
+            }
+            if constexpr (LAST) {
+                v[NVAL - 2] = sg0;
+                v[NVAL - 1] = sg1;
+            }
+            float tot[Bfly<NVAL>::N2];
+            butterfly_sum<NVAL>(v, tot, lane);
+            if (wr) {
+#pragma unroll
+                for (int r = 0; r < Bfly<NVAL>::N2; ++r) {
+                    const int i = butterfly_index<NVAL>(lane & 3, r);
+                    if (i >= 0) {
+                        int dst;
+                        if (i < NR) dst = ELO + i;
+                        else if (i < 2 * NR) dst = NV + ELO + (i - NR);
+                        else if (i < 2 * NR + NIo) dst = NP + OLO + (i - 2 * NR);
+                        else if (i < 2 * NR + 2 * NIo) dst = NV + NP + OLO + (i - 2 * NR - NIo);
+                        else dst = (i == NVAL - 2) ? NV - 1 : 2 * NV - 1;
+                        row[dst] = tot[r];
                     }
                 }
-                PH(tm, tid == 0, LAST ? 14 : 12);
             }
-        };
-        group(std::integral_constant<int, 0>{}, std::integral_constant<int, RS>{}, std::integral_constant<bool, RS == C>{});
-        reload_fence();
-        if constexpr (RS < C)
-            group(std::integral_constant<int, RS>{}, std::integral_constant<int, C>{}, std::integral_constant<bool, true>{});
-        return;
-    }
-    // ---- real parts: sum_t w_k Re(x_i conj x_j), i <= j (class k at k NP + e) ----
-    {
-        float acc[2 * NP];
-#pragma unroll
-        for (int e = 0; e < 2 * NP; ++e) acc[e] = 0.f;
-        static_for<U>([&](auto uc) {
-            constexpr int u = decltype(uc)::value;
-            if (tid + NT * u < T) {
-                cf x[C];
-                getx(uc, x);
-                int e = 0;
-#pragma unroll
-                for (int i = 0; i < C; ++i)
-#pragma unroll
-                    for (int j = i; j < C; ++j) {
-                        const float pr = fmaf(x[i].x, x[j].x, x[i].y * x[j].y);
-                        acc[e] = fmaf(w0[u], pr, acc[e]);
-                        acc[NP + e] = fmaf(w1[u], pr, acc[NP + e]);
-                        ++e;
-                    }
-            }
-            reload_fence();
-        });
-        PH(tm, tid == 0, 11);
-        float tot[Bfly<2 * NP>::N2];
-        butterfly_sum<2 * NP>(acc, tot, lane);
-        if (wr) {
-#pragma unroll
-            for (int r = 0; r < Bfly<2 * NP>::N2; ++r) {
-                const int i = butterfly_index<2 * NP>(lane & 3, r);
-                if (i >= 0) row[(i >= NP ? NV - NP : 0) + i] = tot[r];
-            }
+            PH(tm, tid == 0, LAST ? 14 : 12);
         }
-    }
+    };
+    group(std::integral_constant<int, 0>{}, std::integral_constant<int, RS>{}, std::integral_constant<bool, RS == C>{});
     reload_fence();
-    PH(tm, tid == 0, 12);
-    // ---- imaginary parts, i < j (class k at k NPO + e), and the posterior sums ----
-    {
-        constexpr int NI = 2 * NPO + 2;
-        float acc[NI];
-#pragma unroll
-        for (int e = 0; e < NI; ++e) acc[e] = 0.f;
-        static_for<U>([&](auto uc) {
-            constexpr int u = decltype(uc)::value;
-            if (tid + NT * u < T) {
-                cf x[C];
-                getx(uc, x);
-                int e = 0;
-#pragma unroll
-                for (int i = 0; i < C; ++i)
-#pragma unroll
-                    for (int j = i + 1; j < C; ++j) {
-                        const float pi = fmaf(x[i].y, x[j].x, -x[i].x * x[j].y);
-                        acc[e] = fmaf(w0[u], pi, acc[e]);
-                        acc[NPO + e] = fmaf(w1[u], pi, acc[NPO + e]);
-                        ++e;
-                    }
-            }
-            reload_fence();
-        });
-        PH(tm, tid == 0, 13);
-        acc[2 * NPO] = sg0;
-        acc[2 * NPO + 1] = sg1;
-        float tot[Bfly<NI>::N2];
-        butterfly_sum<NI>(acc, tot, lane);
-        if (wr) {
-#pragma unroll
-            for (int r = 0; r < Bfly<NI>::N2; ++r) {
-                const int i = butterfly_index<NI>(lane & 3, r);
-                if (i >= 0) {
-                    // i < NPO: class 0; i < 2 NPO: class 1; then the two posterior sums
-                    const int dst = i < NPO ? NP + i
-                                            : (i < 2 * NPO ? NV + NP + (i - NPO)
-                                                           : (i == 2 * NPO ? NV - 1 : 2 * NV - 1));
-                    row[dst] = tot[r];
-                }
-            }
-        }
-    }
-    PH(tm, tid == 0, 14);
+    if constexpr (RS < C)
+        group(std::integral_constant<int, RS>{}, std::integral_constant<int, C>{}, std::integral_constant<bool, true>{});
 }
 
 template <int C, int NT, int U, int RF, int WPS>

@@ -20,9 +20,6 @@
 // the chip once, as a partial slab reduced by covar_finalize.
 // Roofline: HBM by construction (4*C*N + 4*T*F bytes per utterance); at C = 8
 // the VALU and LDS work is what is actually felt -- see DESIGN.md section 4/5.
-//
-// Experiment hooks (tools/mk_abl.sh): -DSETK_ONLY_PROD / -DSETK_ONLY_CONS run one
-// role alone, -DSETK_NO_GLOAD skips the audio loads (timing only, wrong results).
 #include "common.h"
 #include "fft512.h"
 #include "covar_fold.h"
@@ -78,7 +75,6 @@ __global__ __launch_bounds__(1024, 4) void stft_covar_kernel(Pass1Args a) {
     const bool ny_active = !DUMP && ny_item >= 0 && ny_item < 2 * NP + 2;
 
     if (wave < 8) {
-#ifndef SETK_ONLY_CONS
         // ================= transform waves =================
         const int la = tid & 15, grp = tid >> 4;
         const int my_set = grp / NF;
@@ -99,13 +95,8 @@ __global__ __launch_bounds__(1024, 4) void stft_covar_kernel(Pass1Args a) {
             const int t = tb_tile + my_tt;
             raw_ok = t < wi.t1;
             raw_last = t == T - 1;
-#ifdef SETK_NO_GLOAD
-            const bool raw_go = raw_ok && n_samp < 0;
-#else
-            const bool raw_go = raw_ok;
-#endif
-            if constexpr (PCM) load_raw_pcm(raw, my_pcm, n_samp, t * a.g.hop - a.g.pad, la, raw_go);
-            else load_raw(raw, my_audio, n_samp, t * a.g.hop - a.g.pad, la, raw_go);
+            if constexpr (PCM) load_raw_pcm(raw, my_pcm, n_samp, t * a.g.hop - a.g.pad, la, raw_ok);
+            else load_raw(raw, my_audio, n_samp, t * a.g.hop - a.g.pad, la, raw_ok);
             if (ny_lane) {
                 raw_ms = 0.f;
                 raw_mn = 0.f;
@@ -160,9 +151,7 @@ __global__ __launch_bounds__(1024, 4) void stft_covar_kernel(Pass1Args a) {
             if (prod) produce(buf ^ 1, tb + TB + NS * TB);
             wg_barrier();
         }
-#endif
     } else {
-#ifndef SETK_ONLY_PROD
         // ================= covariance waves =================
 #pragma unroll
         for (int e = 0; e < ND; ++e) dg_s[e] = dg_n[e] = 0.f;
@@ -254,7 +243,6 @@ __global__ __launch_bounds__(1024, 4) void stft_covar_kernel(Pass1Args a) {
             }
             wg_barrier();
         }
-#endif
     }
 
     if (!DUMP) {

@@ -24,31 +24,6 @@ namespace setk {
 
 constexpr int kMcSlot = 272;  // complex entries per spectrum slot (257 used; 16-byte multiple)
 
-// raw frame samples in the operand layout of mcdft.h: v[e] = x[s + mc::sample_of(lane, e)]
-template <class FloatPtr>
-SETK_DEV void load_raw_mc(float (&v)[8], FloatPtr x, int n_samp, int s, int lane, bool valid) {
-    if (!valid) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = 0.f;
-        return;
-    }
-    const int o = 64 * (lane >> 4) + (lane & 15);  // mc::sample_of(lane, e) = o + 16 e (+ 192 for e >= 4)
-    if (s >= 0 && s + kFrame <= n_samp) {
-        FloatPtr p = x + s + o;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            v[e] = p[16 * e];
-            v[4 + e] = p[256 + 16 * e];
-        }
-    } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            v[e] = x[reflect_index(s + o + 16 * e, n_samp)];
-            v[4 + e] = x[reflect_index(s + o + 256 + 16 * e, n_samp)];
-        }
-    }
-}
-
 template <int C>
 __global__ __launch_bounds__(1024, 4) void stft_covar_mc_kernel(Pass1Args a) {
     constexpr int NT = 1024;
@@ -87,7 +62,6 @@ __global__ __launch_bounds__(1024, 4) void stft_covar_mc_kernel(Pass1Args a) {
     const bool ny_active = ny_item >= 0 && ny_item < 2 * NP + 2;
 
     if (wave < 8) {
-#ifndef SETK_ONLY_CONS
         // ================= transform waves =================
         // C divides 8: G = 8 / C waves per channel, each owns FPW = TB / G CONSECUTIVE frames of
         // a tile.  With hop = 256 consecutive frames share half their samples in the same lane's
@@ -218,9 +192,7 @@ __global__ __launch_bounds__(1024, 4) void stft_covar_mc_kernel(Pass1Args a) {
             if (tb + TB < wi.t1) produce(buf ^ 1, tb + TB);
             wg_barrier();
         }
-#endif
     } else {
-#ifndef SETK_ONLY_PROD
         // ================= covariance waves (as pass1.hip) =================
 #pragma unroll
         for (int e = 0; e < ND; ++e) dg_s[e] = dg_n[e] = 0.f;
@@ -294,7 +266,6 @@ __global__ __launch_bounds__(1024, 4) void stft_covar_mc_kernel(Pass1Args a) {
             }
             wg_barrier();
         }
-#endif
     }
 
     // ---- max |audio| (the renorm target, WaveReader.maxabs) ----

@@ -21,21 +21,14 @@
 namespace setk {
 
 // LDS row stride of this pass: 18 = 16-byte aligned rows, b128 reads (fft512.h), the
-// product at 256 VGPRs; 17 = the 8-byte form pass 1 uses, for tighter register budgets
-#ifndef SETK_P2_ROW
-#define SETK_P2_ROW 18
-#endif
-constexpr int kRow2 = SETK_P2_ROW;
+// product at 256 VGPRs (pass 1 uses the 8-byte form, 17, for its tighter register budget)
+constexpr int kRow2 = 18;
 
-// N consecutive entries of a lane's table row (contiguous for even ROW, 16 apart for odd)
+// N consecutive entries of a lane's table row (contiguous: kRow2 is even)
 template <int N>
 SETK_DEV void load_tab(const cf* row, cf (&out)[N]) {
-    if (LaneTab<kRow2>::rows) {
-        lds_row<N, true>(row, out);
-    } else {
-#pragma unroll
-        for (int n = 0; n < N; ++n) out[n] = row[n * 16];
-    }
+    static_assert(LaneTab<kRow2>::rows, "pass 2 keeps its tables as 16-byte aligned rows");
+    lds_row<N, true>(row, out);
 }
 
 // LDS plan (bytes): slots (16+keep)*2304 (padded 16x16 transpose) | wtab C*257*8 (BF mode) |
@@ -55,7 +48,7 @@ size_t pass2_lds_bytes(int C, int keep) {
 // inverse-transforms and leaves the windowed frame in its LDS slot.  Nothing in
 // that chain needs a workgroup barrier; only the overlap-add does.
 template <int C, bool ISTFT_ONLY>
-__global__ __launch_bounds__(kPass2Threads, SETK_P2_WAVES) void beamform_istft_kernel(Pass2Args a) {
+__global__ __launch_bounds__(kPass2Threads, kPass2WavesPerSimd) void beamform_istft_kernel(Pass2Args a) {
     constexpr int NT = kPass2Threads;
     constexpr int F = kBins;
     constexpr int ST = kSuperTile;

@@ -25,98 +25,28 @@
 
 namespace setk {
 
-// raw frame samples in the operand layout of mcdft.h (pass1_mc.hip)
-template <class FloatPtr>
-SETK_DEV void load_raw_mc2(float (&v)[8], FloatPtr x, int n_samp, int s, int lane, bool valid) {
-    if (!valid) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = 0.f;
-        return;
-    }
-    const int o = 64 * (lane >> 4) + (lane & 15);  // mc::sample_of(lane, e) = o + 16 e (+ 192 for e >= 4)
-    if (s >= 0 && s + kFrame <= n_samp) {
-        FloatPtr p = x + s + o;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            v[e] = p[16 * e];
-            v[4 + e] = p[256 + 16 * e];
-        }
-    } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            v[e] = x[reflect_index(s + o + 16 * e, n_samp)];
-            v[4 + e] = x[reflect_index(s + o + 256 + 16 * e, n_samp)];
-        }
-    }
-}
+// float32 form: two 512-thread workgroups per CU.  16-bit PCM form: ONE 1024-thread workgroup
+// per CU (the tables once instead of twice) whose waves carry the group-boundary half frame of
+// every channel through LDS as packed int16 (8 bytes per lane and channel = 4 KB per wave)
+// instead of re-reading it from HBM at the next group -- the re-read was 1/3 of the kernel's
+// audio traffic (counter traffic 1.35 x algorithmic).  The same carry for float32 samples (16
+// bytes per lane and channel, four channels at most) measured 6.6 % SLOWER in stage 3 at MORE
+// traffic (profiles/rejected/round6_pass2_f32_partial_carry_ab.txt).
+constexpr int kP2McWavesPerSimd = 4;
+constexpr int kP2McGroup = 2;  // R: consecutive frames per group (the carry is written for two)
+constexpr int p2mc_threads(bool pcm) { return pcm ? 1024 : 512; }
 
-#ifndef SETK_P2MC_THREADS
-#define SETK_P2MC_THREADS 512
-#endif
-#ifndef SETK_P2MC_WAVES_PER_SIMD
-#define SETK_P2MC_WAVES_PER_SIMD 4
-#endif
-#ifndef SETK_P2MC_GROUP
-#define SETK_P2MC_GROUP 2
-#endif
-// forward operand tiles in LDS (8 x ds_read_b128 per transform) instead of 32 registers
-#ifndef SETK_P2MC_KLDS
-#define SETK_P2MC_KLDS 1
-#endif
-// ... and the window rows and twiddles too (5 more reads per transform, 20 more registers free)
-#ifndef SETK_P2MC_WLDS
-#define SETK_P2MC_WLDS 1
-#endif
-// streaming (nontemporal) hint on the loads whose data is not read again (see load_full)
-#ifndef SETK_P2MC_NT
-#define SETK_P2MC_NT 1
-#endif
-// samples requested TWO transforms ahead of their use (groups of two frames only): while frame
-// (t0, c) is transformed the whole frame (t0, c + 1) is in flight, and the second half of
-// (t0 + 1, c) landed during the previous transform -- 12 registers in flight instead of 8
-#ifndef SETK_P2MC_PF2
-#define SETK_P2MC_PF2 0
-#endif
-// 16-bit PCM form: ONE 1024-thread workgroup per CU (the tables once instead of twice) whose waves
-// carry the group-boundary half frame of every channel through LDS as packed int16 (8 bytes per
-// lane and channel = 4 KB per wave) instead of re-reading it from HBM at the next group -- the
-// re-read was 1/3 of the kernel's audio traffic (counter traffic 1.35 x algorithmic).
-#ifndef SETK_P2MC_PCM_THREADS
-#define SETK_P2MC_PCM_THREADS 1024
-#endif
-#ifndef SETK_P2MC_PCM_CARRY
-#define SETK_P2MC_PCM_CARRY 1
-#endif
-// float32 form: the same carry for the first SETK_P2MC_F32_CARRY_CH channels only (16 bytes per
-// lane and channel: four channels are the 4 KB per wave that fit), 1024-thread workgroups; 0 = the
-// two-workgroup form without a carry -- the default: with 4 the 8-channel kernel holds two load
-// paths (24 spilled registers) and measured 6.6 % SLOWER in stage 3 at MORE traffic (1.37 x against
-// 1.31 x; profiles/rejected/round6_pass2_f32_partial_carry_ab.txt)
-#ifndef SETK_P2MC_F32_CARRY_CH
-#define SETK_P2MC_F32_CARRY_CH 0
-#endif
-struct False { static constexpr bool value = false; };
-struct True { static constexpr bool value = true; };
-constexpr int kP2McThreads = SETK_P2MC_THREADS;
-constexpr int kP2McPcmThreads = SETK_P2MC_PCM_THREADS;
-constexpr bool kP2McPcmCarry = SETK_P2MC_PCM_CARRY != 0;
-constexpr int kP2McF32CarryCh = SETK_P2MC_F32_CARRY_CH;
-constexpr int p2mc_threads(bool pcm) { return pcm ? kP2McPcmThreads : (kP2McF32CarryCh > 0 ? 1024 : kP2McThreads); }
-// channels whose group-boundary half frame a wave carries through LDS, and the bytes per lane
-constexpr int p2mc_carry_ch(int C, bool pcm) {
-    return pcm ? (kP2McPcmCarry ? C : 0) : (C < kP2McF32CarryCh ? C : kP2McF32CarryCh);
-}
-constexpr int p2mc_carry_bytes(bool pcm) { return pcm ? 8 : 16; }
-
-constexpr int kP2McTiles = SETK_P2MC_KLDS ? (SETK_P2MC_WLDS ? 25 : 20) : 12;  // BR_H .. IT_L (10 tiles, contiguous words) + OT_H, OT_L + the forward's 8
+// forward operand tiles, window rows and twiddles in LDS: BR_H .. IT_L (10 tiles, contiguous
+// words) + OT_H, OT_L + the forward's 8 + window 2 + twiddles 3
+constexpr int kP2McTiles = 25;
 // LDS plan (bytes): wtab C * 257 * 8 | operand tiles 25 * 1024 | synthesis rows
 // 2048 | a16 scratch NW * 8 * kOddPitch * 4 | yodd NW * 16 * 4 | red 64
 // | PCM carry NW * C * 64 * 8
 size_t pass2_mc_lds_bytes(int C, bool pcm) {
     const size_t nw = p2mc_threads(pcm) / 64;
     const size_t wt = ((size_t)C * kBins * sizeof(cf) + 15) & ~(size_t)15;
-    return wt + kP2McTiles * 1024 + 2048 + nw * SETK_P2MC_GROUP * 8 * mc::kOddPitch * sizeof(float) +
-           nw * 16 * sizeof(float) + 64 + nw * p2mc_carry_ch(C, pcm) * 64 * p2mc_carry_bytes(pcm);
+    return wt + kP2McTiles * 1024 + 2048 + nw * kP2McGroup * 8 * mc::kOddPitch * sizeof(float) +
+           nw * 16 * sizeof(float) + 64 + (pcm ? nw * C * 64 * sizeof(uint2) : 0);
 }
 
 // sum over the first 8 lanes of every 16-lane row, result in lanes 0..7 of the row
@@ -160,29 +90,28 @@ SETK_DEV float wave_max_nonneg(float x) {
 // PCM: UttDesc::audio is planar 16-bit PCM (kAudioPcm16) -- sign-extending 2-byte loads, one
 // conversion per sample, and 2^-15 (read_wav's int16 / 32768) folded into the window rows.
 template <int C, bool PCM = false>
-__global__ __launch_bounds__(p2mc_threads(PCM), SETK_P2MC_WAVES_PER_SIMD) void beamform_istft_mc_kernel(Pass2Args a) {
+__global__ __launch_bounds__(p2mc_threads(PCM), kP2McWavesPerSimd) void beamform_istft_mc_kernel(Pass2Args a) {
     constexpr int NT = p2mc_threads(PCM);
     constexpr int NW = NT / 64;
     constexpr int F = kBins;
-    constexpr int CC = p2mc_carry_ch(C, PCM);   // channels 0 .. CC - 1 are carried
-    constexpr bool CARRY = CC > 0;
-    typedef typename std::conditional<PCM, uint2, mc::f4>::type carry_t;
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* p = smem;
     cf* wtab = reinterpret_cast<cf*>(p);  // [C][257]
     p += ((size_t)C * F * sizeof(cf) + 15) & ~(size_t)15;
-    mc::u4* tiles = reinterpret_cast<mc::u4*>(p);  // [12][64]: BR_H BR_L BI_H BI_L G0_H G0_L G1_H G1_L IT_H IT_L OT_H OT_L
+    // [25][64]: BR_H BR_L BI_H BI_L G0_H G0_L G1_H G1_L IT_H IT_L OT_H OT_L | the forward's 8 |
+    // window rows 0..3, 4..7 | TR TI TRI
+    mc::u4* tiles = reinterpret_cast<mc::u4*>(p);
     p += kP2McTiles * 1024;
     mc::f4* synr = reinterpret_cast<mc::f4*>(p);  // [2][64] float4: synthesis rows 0..3 / 4..7 of a lane
     p += 2048;
     float* a16s = reinterpret_cast<float*>(p);  // [NW][R][8][kOddPitch]
-    p += (size_t)NW * SETK_P2MC_GROUP * 8 * mc::kOddPitch * sizeof(float);
+    p += (size_t)NW * kP2McGroup * 8 * mc::kOddPitch * sizeof(float);
     float* yodd_s = reinterpret_cast<float*>(p);  // [NW][16]
     p += NW * 16 * sizeof(float);
     float* red = reinterpret_cast<float*>(p);
     p += 64;
-    carry_t* carry_s = reinterpret_cast<carry_t*>(p);  // [NW][CC][64]: packed int16 x 4 / float x 4
+    uint2* carry_s = reinterpret_cast<uint2*>(p);  // PCM: [NW][C][64] packed int16 x 4
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -222,9 +151,7 @@ __global__ __launch_bounds__(p2mc_threads(PCM), SETK_P2MC_WAVES_PER_SIMD) void b
     }
     mc::stage_tiles(tiles, a.mc_tab, mc::kW_BR_H, 10, tid, NT);
     mc::stage_tiles(tiles + 10 * 64, a.mc_tab, mc::kW_OT_H, 2, tid, NT);
-#if SETK_P2MC_KLDS
     mc::stage_tiles(tiles + 12 * 64, a.mc_tab, mc::kW_MC_H, 8, tid, NT);
-#if SETK_P2MC_WLDS
     for (int i = tid; i < 128; i += NT) {
         const int l = i & 63, t4 = i >> 6;
         const mc::f4 w = {a.mc_win[(4 * t4 + 0) * 64 + l] * in_sc, a.mc_win[(4 * t4 + 1) * 64 + l] * in_sc,
@@ -232,32 +159,12 @@ __global__ __launch_bounds__(p2mc_threads(PCM), SETK_P2MC_WAVES_PER_SIMD) void b
         tiles[20 * 64 + i] = __builtin_bit_cast(mc::u4, w);
     }
     mc::stage_tiles(tiles + 22 * 64, a.mc_tab, mc::kW_TR, 3, tid, NT);
-#endif
-#endif
     for (int i = tid; i < 128; i += NT) {
         const int l = i & 63, hf = i >> 6;
         synr[i] = (mc::f4){a.mc_syn[(4 * hf + 0) * 64 + l] * out_sc, a.mc_syn[(4 * hf + 1) * 64 + l] * out_sc,
                            a.mc_syn[(4 * hf + 2) * 64 + l] * out_sc, a.mc_syn[(4 * hf + 3) * 64 + l] * out_sc};
     }
-#if SETK_P2MC_KLDS && SETK_P2MC_WLDS
     struct { float tr[4], ti[4]; } K;  // (the inverse's conjugate twiddles: re-read there)
-#elif SETK_P2MC_KLDS
-    struct { float tr[4], ti[4], tri[4]; } K;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        K.tr[r] = mc::tab_f(a.mc_tab, mc::kW_TR + r, lane);
-        K.ti[r] = mc::tab_f(a.mc_tab, mc::kW_TI + r, lane);
-        K.tri[r] = mc::tab_f(a.mc_tab, mc::kW_TRI + r, lane);
-    }
-#else
-    mc::Fwd K;
-    mc::load_fwd(K, a.mc_tab, lane);
-#endif
-#if !(SETK_P2MC_KLDS && SETK_P2MC_WLDS)
-    float win[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) win[e] = gptr(a.mc_win)[e * 64 + lane] * in_sc;
-#endif
     float* yoddw = yodd_s + wave * 16;
     const int lane_bin = mc::bin_of(c16, g, 0);
     const cf* wl = wtab + lane_bin;                       // + c * F + 32 r
@@ -278,7 +185,7 @@ __global__ __launch_bounds__(p2mc_threads(PCM), SETK_P2MC_WAVES_PER_SIMD) void b
     // its first half with frame t -- the same lane's registers (mc::sample_of) -- so inside a
     // group a transform loads four new samples per lane, not eight, and the weights of a channel
     // are read once per group.  The R spectra of the group accumulate in registers.
-    constexpr int R = SETK_P2MC_GROUP;
+    constexpr int R = kP2McGroup;
     float* a16g = a16s + wave * R * 8 * mc::kOddPitch;  // [R][8 channels][kOddPitch]
     float carry[4] = {0.f, 0.f, 0.f, 0.f};
     // loaders: a whole frame (8 registers) / the second half of a frame (registers 4..7).
@@ -291,111 +198,64 @@ __global__ __launch_bounds__(p2mc_threads(PCM), SETK_P2MC_WAVES_PER_SIMD) void b
         if constexpr (PCM) return (gcshort_p)gptr(ud.audio) + (size_t)c * ud.ch_stride;
         else return gptr(ud.audio) + (size_t)c * n_samp;
     };
-    // CARRY: the lane's own four samples of the half frame a group ends with, per channel -- a
-    // thread reads back exactly what it wrote (program order suffices, no barrier)
-    carry_t* carry_l = carry_s + (size_t)wave * CC * 64 + lane;  // + 64 c
-    auto load_full = [&](float (&v)[8], int t, int c, auto edge, bool first) __attribute__((always_inline)) {
-        (void)first;
-        if constexpr (CARRY) {
+    // PCM carry: the lane's own four samples of the half frame a group ends with, per channel --
+    // a thread reads back exactly what it wrote (program order suffices, no barrier)
+    uint2* carry_l = carry_s + (size_t)wave * C * 64 + lane;  // + 64 c
+    auto load_full = [&](float (&v)[8], int t, int c, auto edge) __attribute__((always_inline)) {
+        if constexpr (PCM) {
             // first half: what this lane parked at the end of the previous group (or the prefill
             // before the first); second half: the only samples of the frame not seen yet
-            if (CC == C || c < CC) {
-                if constexpr (PCM) {
-                    const uint2 pk = carry_l[64 * c];
-                    v[0] = (float)(short)(pk.x & 0xffff);
-                    v[1] = (float)((int)pk.x >> 16);
-                    v[2] = (float)(short)(pk.y & 0xffff);
-                    v[3] = (float)((int)pk.y >> 16);
-                } else {
-                    const mc::f4 pk = carry_l[64 * c];
+            const uint2 pk = carry_l[64 * c];
+            v[0] = (float)(short)(pk.x & 0xffff);
+            v[1] = (float)((int)pk.x >> 16);
+            v[2] = (float)(short)(pk.y & 0xffff);
+            v[3] = (float)((int)pk.y >> 16);
+            const auto x = chan(c);
+            const int s0 = min(t, T - 1) * hop - a.g.pad + 256, o = 64 * g + c16;
+            if (!decltype(edge)::value) {
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = pk[e];
-                }
-#ifdef SETK_P2MC_ABL_L2  // ablation: every wave reads the same 1 MB (L2 resident) -- wrong results
-                const auto x = (gcshort_p)gptr(a.utts[0].audio) + (size_t)c * a.utts[0].ch_stride;
-                const int s0 = (min(t, T - 1) & 127) * hop + 4096 + 256, o = 64 * g + c16;
-#else
-                const auto x = chan(c);
-                const int s0 = min(t, T - 1) * hop - a.g.pad + 256, o = 64 * g + c16;
-#endif
-                if (!decltype(edge)::value) {
+                for (int e = 0; e < 4; ++e) v[4 + e] = x[s0 + o + 16 * e];
+            } else {
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) v[4 + e] = x[s0 + o + 16 * e];
-                } else {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[4 + e] = x[reflect_index(s0 + o + 16 * e, n_samp)];
-                }
-                return;
+                for (int e = 0; e < 4; ++e) v[4 + e] = x[reflect_index(s0 + o + 16 * e, n_samp)];
             }
-        }
-#ifdef SETK_P2MC_ABL_L2  // ablation: every wave reads the same 1 MB (L2 resident) -- wrong results
-        gcfloat_p x = gptr(a.utts[0].audio) + (size_t)c * n_samp;
-        (void)chan;
-        const int s0 = (min(t, T - 1) & 127) * hop + 4096, o = 64 * g + c16;
-#else
-        const auto x = chan(c);
-        const int s0 = min(t, T - 1) * hop - a.g.pad, o = 64 * g + c16;
-#endif
-        if (!decltype(edge)::value) {
+        } else {
+            const auto x = chan(c);
+            const int s0 = min(t, T - 1) * hop - a.g.pad, o = 64 * g + c16;
+            if (!decltype(edge)::value) {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-#if SETK_P2MC_NT
-                // (float32 samples only: on the 2-byte loads of the PCM form the hint measured
-                //  0.4 - 2.5 % slower, profiles/round5_pass2_nt_pf2_ab.txt)
-                // both halves of a group's first frame are read for the last time here (the first
-                // one is the re-read of what the previous group fetched as ITS last half): a
-                // streaming hint keeps them from pushing the halves that WILL be read again --
-                // load_half's -- out of the XCD's L2
-                if constexpr (PCM) {
-                    v[e] = x[s0 + o + 16 * e];
-                    v[4 + e] = x[s0 + o + 256 + 16 * e];
-                } else {
+                for (int e = 0; e < 4; ++e) {
+                    // both halves of a group's first frame are read for the last time here (the
+                    // first one is the re-read of what the previous group fetched as ITS last
+                    // half): a streaming hint keeps them from pushing the halves that WILL be read
+                    // again -- load_half's -- out of the XCD's L2
                     v[e] = __builtin_nontemporal_load(&x[s0 + o + 16 * e]);
                     v[4 + e] = __builtin_nontemporal_load(&x[s0 + o + 256 + 16 * e]);
                 }
-#else
-                v[e] = x[s0 + o + 16 * e];
-                v[4 + e] = x[s0 + o + 256 + 16 * e];
-#endif
-            }
-        } else {
+            } else {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                v[e] = x[reflect_index(s0 + o + 16 * e, n_samp)];
-                v[4 + e] = x[reflect_index(s0 + o + 256 + 16 * e, n_samp)];
+                for (int e = 0; e < 4; ++e) {
+                    v[e] = x[reflect_index(s0 + o + 16 * e, n_samp)];
+                    v[4 + e] = x[reflect_index(s0 + o + 256 + 16 * e, n_samp)];
+                }
             }
         }
     };
-    // the same half as raw 16-bit samples (CARRY): converted and packed for the carry where consumed
+    // PCM: the second half as raw 16-bit samples, converted and packed for the carry where consumed
     auto load_half_raw = [&](int (&r)[4], int t, int c, auto edge) __attribute__((always_inline)) {
-        if constexpr (PCM) {
-#ifdef SETK_P2MC_ABL_L2
-            const auto x = (gcshort_p)gptr(a.utts[0].audio) + (size_t)c * a.utts[0].ch_stride;
-            const int s0 = (min(t, T - 1) & 127) * hop + 4096 + 512, o = 64 * g + c16;
-#else
-            const auto x = chan(c);
-            const int s0 = min(t, T - 1) * hop - a.g.pad + 256, o = 64 * g + c16;
-#endif
-            if (!decltype(edge)::value) {
+        const auto x = chan(c);
+        const int s0 = min(t, T - 1) * hop - a.g.pad + 256, o = 64 * g + c16;
+        if (!decltype(edge)::value) {
 #pragma unroll
-                for (int e = 0; e < 4; ++e) r[e] = x[s0 + o + 16 * e];
-            } else {
+            for (int e = 0; e < 4; ++e) r[e] = x[s0 + o + 16 * e];
+        } else {
 #pragma unroll
-                for (int e = 0; e < 4; ++e) r[e] = x[reflect_index(s0 + o + 16 * e, n_samp)];
-            }
+            for (int e = 0; e < 4; ++e) r[e] = x[reflect_index(s0 + o + 16 * e, n_samp)];
         }
     };
     auto load_half = [&](float (&v)[8], int t, int c, auto edge) __attribute__((always_inline)) {
-#ifdef SETK_P2MC_ABL_REHALF  // ablation: re-read the half just loaded (cache hit) -- wrong results
-        const auto x = chan(c);
-        const int s0 = min(t, T - 1) * hop - a.g.pad, o = 64 * g + c16;
-#elif defined(SETK_P2MC_ABL_L2)
-        gcfloat_p x = gptr(a.utts[0].audio) + (size_t)c * n_samp;
-        const int s0 = (min(t, T - 1) & 127) * hop + 4096 + 256, o = 64 * g + c16;
-#else
         const auto x = chan(c);
         const int s0 = min(t, T - 1) * hop - a.g.pad + 256, o = 64 * g + c16;
-#endif
         if (!decltype(edge)::value) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[4 + e] = x[s0 + o + 16 * e];
@@ -404,28 +264,12 @@ __global__ __launch_bounds__(p2mc_threads(PCM), SETK_P2MC_WAVES_PER_SIMD) void b
             for (int e = 0; e < 4; ++e) v[4 + e] = x[reflect_index(s0 + o + 16 * e, n_samp)];
         }
     };
-#if SETK_P2MC_PF2
-    static_assert(SETK_P2MC_GROUP == 2, "the two-ahead prefetch is written for groups of two frames");
-    float nxth[4];  // second half of frame t0 + 1 of the NEXT channel
-    auto load_half4 = [&](float (&v)[4], int t, int c, auto edge) __attribute__((always_inline)) {
-        const auto x = chan(c);
-        const int s0 = min(t, T - 1) * hop - a.g.pad + 256, o = 64 * g + c16;
-        if (!decltype(edge)::value) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = x[s0 + o + 16 * e];
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = x[reflect_index(s0 + o + 16 * e, n_samp)];
-        }
-    };
-#endif
     mc::f4 yr[R], yi[R];
     // the R transforms of every channel of one group; `nxt` arrives holding frame (t0, channel 0)
     // and leaves holding frame (t0 + R, channel 0)
     float nxt[8];
-    int nraw[4];  // CARRY: the half frame in flight, as loaded
-    auto group = [&](int t0, auto edge, bool first_next) __attribute__((always_inline)) {
-        (void)first_next;
+    int nraw[4];  // PCM: the half frame in flight, as loaded
+    auto group = [&](int t0, auto edge) __attribute__((always_inline)) {
 #pragma unroll
         for (int k = 0; k < R; ++k) {
             yr[k] = (mc::f4){0.f, 0.f, 0.f, 0.f};
@@ -441,32 +285,17 @@ __global__ __launch_bounds__(p2mc_threads(PCM), SETK_P2MC_WAVES_PER_SIMD) void b
             float x[8];
 #pragma unroll
             for (int e = 0; e < 8; ++e) x[e] = nxt[e];
-#if SETK_P2MC_PF2
-            float xh[4];  // this channel's second half of frame t0 + 1 (requested one channel ago)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) xh[e] = nxth[e];
-#endif
 #pragma unroll
             for (int k = 0; k < R; ++k) {
-#if SETK_P2MC_PF2
-                // two transforms ahead: during (t0, c) the whole frame (t0, c + 1), during
-                // (t0 + 1, c) the second half of (t0 + 1, c + 1)
-                if (c + 1 < C) {
-                    if (k == 0) load_full(nxt, t0, c + 1, edge, true);
-                    else load_half4(nxth, t0 + 1, c + 1, edge);
-                }
-#else
                 // what comes next travels while this transform runs: the second half of the
                 // next frame of the group, or the first frame of the next channel / group
                 if (k + 1 < R) {
-                    if constexpr (CARRY && PCM) load_half_raw(nraw, t0 + k + 1, c, edge);
+                    if constexpr (PCM) load_half_raw(nraw, t0 + k + 1, c, edge);
                     else load_half(nxt, t0 + k + 1, c, edge);
                 } else if (c + 1 < C) {
-                    load_full(nxt, t0, c + 1, edge, first_next);
+                    load_full(nxt, t0, c + 1, edge);
                 }
-#endif
                 mc::f4 zr, zi, a16;
-#if SETK_P2MC_KLDS && SETK_P2MC_WLDS
                 {
                     asm volatile("" ::: "memory");
                     const mc::f4 w0 = __builtin_bit_cast(mc::f4, tiles[20 * 64 + lane]);
@@ -479,11 +308,6 @@ __global__ __launch_bounds__(p2mc_threads(PCM), SETK_P2MC_WAVES_PER_SIMD) void b
                                 tri[4] = {q2[0], q2[1], q2[2], q2[3]};
                     mc::forward_t(x, win, [&](int i) { return mc::lds_h8(tiles, 12 + i, lane); }, tr, ti, tri, zr, zi, a16);
                 }
-#elif SETK_P2MC_KLDS
-                mc::forward_t(x, win, [&](int i) { return mc::lds_h8(tiles, 12 + i, lane); }, K.tr, K.ti, K.tri, zr, zi, a16);
-#else
-                mc::forward(x, win, K, zr, zi, a16);
-#endif
                 mc::store_a16(a16g + k * 8 * mc::kOddPitch, c, lane, a16);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
@@ -494,22 +318,14 @@ __global__ __launch_bounds__(p2mc_threads(PCM), SETK_P2MC_WAVES_PER_SIMD) void b
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         x[e] = x[4 + e];
-#if SETK_P2MC_PF2
-                        x[4 + e] = xh[e];
-#else
-                        if constexpr (CARRY && PCM) x[4 + e] = (float)nraw[e];
+                        if constexpr (PCM) x[4 + e] = (float)nraw[e];
                         else x[4 + e] = nxt[4 + e];
-#endif
                     }
-                    if constexpr (CARRY) {
+                    if constexpr (PCM) {
                         // the group's last half frame is the next group's first: R == 2, k == 0
-                        static_assert(!CARRY || R == 2, "the LDS carry is written for groups of two frames");
-                        if constexpr (PCM) {
-                            carry_l[64 * c] = make_uint2(__builtin_amdgcn_perm((unsigned)nraw[1], (unsigned)nraw[0], 0x05040100u),
-                                                         __builtin_amdgcn_perm((unsigned)nraw[3], (unsigned)nraw[2], 0x05040100u));
-                        } else if (CC == C || c < CC) {
-                            carry_l[64 * c] = (mc::f4){nxt[4], nxt[5], nxt[6], nxt[7]};
-                        }
+                        static_assert(R == 2, "the LDS carry is written for groups of two frames");
+                        carry_l[64 * c] = make_uint2(__builtin_amdgcn_perm((unsigned)nraw[1], (unsigned)nraw[0], 0x05040100u),
+                                                     __builtin_amdgcn_perm((unsigned)nraw[3], (unsigned)nraw[2], 0x05040100u));
                     }
                 }
                 // one transform at a time: interleaved by the scheduler, the R unrolled
@@ -522,51 +338,35 @@ __global__ __launch_bounds__(p2mc_threads(PCM), SETK_P2MC_WAVES_PER_SIMD) void b
         const int lo = t0 * hop - a.g.pad, hi = (t0 + R - 1) * hop - a.g.pad + kNfft;
         return lo < 0 || hi > n_samp || t0 + R > T;
     };
-    auto request_group = [&](int t0, bool first) __attribute__((always_inline)) {
-        if (span_is_edge(t0)) {
-            load_full(nxt, t0, 0, True(), first);
-#if SETK_P2MC_PF2
-            load_half4(nxth, t0 + 1, 0, True());
-#endif
-        } else {
-            load_full(nxt, t0, 0, False(), first);
-#if SETK_P2MC_PF2
-            load_half4(nxth, t0 + 1, 0, False());
-#endif
-        }
+    auto request_group = [&](int t0) __attribute__((always_inline)) {
+        if (span_is_edge(t0)) load_full(nxt, t0, 0, std::true_type());
+        else load_full(nxt, t0, 0, std::false_type());
     };
-    if constexpr (CARRY) {
+    if constexpr (PCM) {
         // the first half of the wave's first frame, every channel: from here on a group reads two
         // half frames per channel from HBM, never three
         if (tw < tb) {
 #pragma unroll 1
-            for (int c = 0; c < CC; ++c) {
+            for (int c = 0; c < C; ++c) {
                 const auto x = chan(c);
                 const int s0 = tw * hop - a.g.pad, o = 64 * g + c16;
-                if constexpr (PCM) {
-                    int r[4];
+                int r[4];
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) r[e] = x[reflect_index(s0 + o + 16 * e, n_samp)];
-                    carry_l[64 * c] = make_uint2(__builtin_amdgcn_perm((unsigned)r[1], (unsigned)r[0], 0x05040100u),
-                                                 __builtin_amdgcn_perm((unsigned)r[3], (unsigned)r[2], 0x05040100u));
-                } else {
-                    mc::f4 r;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) r[e] = x[reflect_index(s0 + o + 16 * e, n_samp)];
-                    carry_l[64 * c] = r;
-                }
+                for (int e = 0; e < 4; ++e) r[e] = x[reflect_index(s0 + o + 16 * e, n_samp)];
+                carry_l[64 * c] = make_uint2(__builtin_amdgcn_perm((unsigned)r[1], (unsigned)r[0], 0x05040100u),
+                                             __builtin_amdgcn_perm((unsigned)r[3], (unsigned)r[2], 0x05040100u));
             }
         }
     }
-    if (tw < tb) request_group(tw, true);
+    if (tw < tb) request_group(tw);
 #pragma unroll 1
     for (int t0 = tw; t0 < tb; t0 += R) {
         const int nf = min(R, tb - t0);
         // (the channels 1.. of this group are fetched inside it: from the carry unless it is the
         //  wave's first group)
-        if (span_is_edge(t0)) group(t0, True(), t0 == tw);
-        else group(t0, False(), t0 == tw);
-        if (t0 + R < tb) request_group(t0 + R, false);  // (issued here: its span decides the path)
+        if (span_is_edge(t0)) group(t0, std::true_type());
+        else group(t0, std::false_type());
+        if (t0 + R < tb) request_group(t0 + R);  // (issued here: its span decides the path)
 #pragma unroll
         for (int k = 0; k < R; ++k) {
             if (k >= nf) break;
@@ -637,7 +437,6 @@ __global__ __launch_bounds__(p2mc_threads(PCM), SETK_P2MC_WAVES_PER_SIMD) void b
                 fi[r] *= sc;
             }
             float bmid[8];
-#if SETK_P2MC_KLDS && SETK_P2MC_WLDS
             {
                 const mc::f4 tt0 = __builtin_bit_cast(mc::f4, tiles[22 * 64 + lane]);
                 const mc::f4 tt1 = __builtin_bit_cast(mc::f4, tiles[23 * 64 + lane]);
@@ -647,7 +446,6 @@ __global__ __launch_bounds__(p2mc_threads(PCM), SETK_P2MC_WAVES_PER_SIMD) void b
                     K.ti[r] = tt1[r];
                 }
             }
-#endif
             mc::inverse_a(fr, fi, e16, mc::lds_h8(tiles, 0, lane), mc::lds_h8(tiles, 1, lane),
                           mc::lds_h8(tiles, 2, lane), mc::lds_h8(tiles, 3, lane), K.tr, K.ti, bmid, lane);
             asm volatile("" ::: "memory");
@@ -706,7 +504,7 @@ __global__ __launch_bounds__(p2mc_threads(PCM), SETK_P2MC_WAVES_PER_SIMD) void b
 
 // workgroups of this kernel a CU holds (registers and LDS), for the work-list cut of capi.hip
 int pass2_mc_wgs_per_cu(int C, bool pcm) {
-    const int by_waves = SETK_P2MC_WAVES_PER_SIMD * 4 / (p2mc_threads(pcm) / 64);
+    const int by_waves = kP2McWavesPerSimd * 4 / (p2mc_threads(pcm) / 64);
     const int by_lds = (int)((160u << 10) / pass2_mc_lds_bytes(C, pcm));
     return by_waves < by_lds ? (by_waves > 0 ? by_waves : 1) : (by_lds > 0 ? by_lds : 1);
 }

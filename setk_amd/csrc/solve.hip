@@ -222,14 +222,11 @@ SD bool jacobi_round_f32(float2 (&g)[C], int j, float floor2) {
     return false;
 }
 
-#ifndef SETK_SOLVE_FP64_ONLY
-#define SETK_SOLVE_FP64_ONLY 0
-#endif
 // a[i] = A[i][j] (lane j owns column j of the Hermitian PSD A, 8 lanes per problem)
 template <int C>
 SD void pevd_mixed(const cd (&a)[C], int j, cd (&out)[C], double& lam, int& noconv) {
     constexpr int W = Grp<C>::W;
-    if constexpr (W > 8 || SETK_SOLVE_FP64_ONLY) {
+    if constexpr (W > 8) {
         cd g[C];
 #pragma unroll
         for (int i = 0; i < C; ++i) g[i] = a[i];
@@ -471,11 +468,8 @@ SD void gev_vector(const cd (&rs)[C], const cd* L, cd* Wk, int j, bool gauge, cd
 // stage of the 125 x 257-bin MVDR batch.  Forcing 3 or 4 waves per SIMD
 // (168 / 128 VGPRs, spilling the eigenvector across the Cholesky) measured the
 // same time, so the budget stays at 2.
-#ifndef SETK_SOLVE_WAVES
-#define SETK_SOLVE_WAVES 2
-#endif
 template <int C, int KIND>
-__global__ __launch_bounds__(64, (C > 8) ? 1 : SETK_SOLVE_WAVES) void solve_kernel(SolveArgs a, int pitch, int lds_mats) {
+__global__ __launch_bounds__(64, (C > 8) ? 1 : 2) void solve_kernel(SolveArgs a, int pitch, int lds_mats) {
     constexpr int NP = npairs(C);
     constexpr int W = Grp<C>::W;   // lanes per problem
     constexpr int PW = 64 / W;     // problems per wavefront (= workgroup)

@@ -7,8 +7,7 @@
 # + SQ_WAIT_INST_ANY   (issue stall: the instruction is ready, its pipe is not -- LDS sub-bucket)
 # + SQ_WAIT_ANY        (parked: s_waitcnt on memory / LDS returns, s_barrier)
 # (MI355X_MICROARCH.md, "rocprofv3 PMC slots": the three are disjoint and sum to WAVE_CYCLES).
-# Run for the default build and for the single-role builds of pass 1 (transform waves only /
-# covariance waves only, tools/mk_abl.sh -DSETK_ONLY_PROD / -DSETK_ONLY_CONS), counters only,
+# Run for the default build and for any variant builds given (tools/mk_abl.sh), counters only,
 # one pass per group.   bash tools/stall_table.sh <tag> [lib ...]
 set -u
 TAG=${1:-r5}; shift || true
