@@ -57,7 +57,8 @@ extern "C" {
 #define SETK_NUM_OK 0
 #define SETK_NUM_SINGULAR 1 /* noise covariance not positive definite        */
 #define SETK_NUM_NOCONV 2   /* Jacobi sweep limit reached                    */
-#define SETK_NUM_NONFINITE 3
+#define SETK_NUM_NONFINITE 3 /* NaN / inf in this bin's input (reported even where it also makes the
+                              factorisation fail), or a non-finite result of finite input   */
 #define SETK_NUM_RANKDEF 4  /* WPE only, NOT an error: the tap correlation was rank deficient
                               (fewer frames than channels x taps, a silent or duplicated channel),
                               columns at the noise level were dropped and a filter was produced;

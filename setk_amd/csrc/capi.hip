@@ -1019,8 +1019,8 @@ int setk_covar(setk_handle_t h, const float* spec, const float* mask, int num_ch
 static int run_weights(setk_handle_t h, const setk_bf_opts& o, int kind, const float* Rs,
                        const float* Rn, const float* Ry, int F, int C_in, float* weight,
                        int* status, int* ref_out, hipStream_t s) {
-    // 8 < C <= 16: embedded in 16 x 16 problems, blkdiag(Rs, 0) / blkdiag(Rn, I): same
-    // solution in the first C components, 16 lanes per problem (solve.hip)
+    // 8 < C <= 16: embedded in 16 x 16 problems, blkdiag(Rs, 0) / blkdiag(Rn, max diag(Rn) I):
+    // same solution in the first C components, 16 lanes per problem (solve.hip)
     const int C = C_in > kMaxChannels ? kMaxChannels16 : C_in;
     const int NP = npairs(C);
     const int pitch = pitch_of(F);
@@ -2165,8 +2165,8 @@ int setk_enhance_batch_taps(setk_handle_t h, const setk_bf_opts* opts, int n_utt
     fa.num_scale = mc1 ? (float)((h->mc_peak / 1024.0) * (h->mc_peak / 1024.0)) : 1.f;
     // With a few slabs per utterance (the shard of the bench: two) the solve sums them itself and
     // this launch -- 26 us of an 87 us stage, mostly launch and tail -- falls away.  Not when the
-    // covariances are tapped, not for PMWF's reference search (pmwf_select_kernel reads Rn back
-    // for BAN), not for long utterances (32 slabs: the parallel reduction is the better one).
+    // covariances are tapped, not for PMWF's reference search (never measured fused; its
+    // select kernel used to read Rn back for BAN), not for long utterances (32 slabs: the parallel reduction is the better one).
     const bool fuse_reduce = !(taps && (taps->Rs || taps->Rn)) && max_parts <= 4 &&
                              !(kind == SETK_BF_PMWF && opts->pmwf_ref < 0) &&
                              !(getenv("SETK_FUSED_REDUCE") && atoi(getenv("SETK_FUSED_REDUCE")) == 0);

@@ -15,8 +15,14 @@
 //   * the generalised problem is reduced with the Cholesky factor
 //     (C~ = L^-1 Rs L^-H), solved by the same Jacobi and back-substituted.
 // The kernel is latency bound and negligible in bytes/flops next to the two
-// streaming passes; fp64 keeps it at least as accurate as the reference's
-// LAPACK c64/c128 calls.
+// streaming passes.  Measured against the reference evaluated in complex128 on constructed
+// families (tests/test_gpu_solve.py, tests/PARITY_NOTES.md "Solver conformance"): every
+// operation, 1..16 channels, eigenvalue gaps from 0.9 down to 1e-3, cond(Rn) up to 1e5 and
+// input scales 2^-80 .. 2^80 stay within 8 eps32 + 2 s of it, s being how far that reference
+// moves when its float32 inputs move by half an ulp; the residual |A v - theta v| of the plain
+// eigenvector is below 1 eps32 |A| per matrix.  (numpy's eigh and solve compute in double even
+// on complex64 input; only scipy's pencil solve runs a complex64 driver, and it loses
+// eps32 * cond(Rn), which this kernel does not.)
 #include "common.h"
 #include "dpp.h"
 #include <hip/hip_runtime.h>
@@ -62,17 +68,22 @@ SD bool jacobi_round(cd (&g)[C], int j, double floor2) {
     const double tol2 = 1e-16;  // see jacobi_pevd
     const int p = j ^ M;
     cd gp[C];
-    double m = 0.0, o = 0.0;
+    double m = 0.0, o = 0.0, dyb = 0.0;
     cd d = make_double2(0.0, 0.0);
+    // (explicit fma chains that the partner lane reproduces bit for bit with g and gp swapped, so
+    //  that both take the same decision: see jacobi_round_f32)
 #pragma unroll
     for (int i = 0; i < C; ++i) {
         gp[i] = make_double2(dshfl_xor<M>(g[i].x), dshfl_xor<M>(g[i].y));
-        m += zabs2(g[i]);
-        o += zabs2(gp[i]);
-        d = zadd(d, zcmul(g[i], gp[i]));
+        m = fma(g[i].x, g[i].x, fma(g[i].y, g[i].y, m));
+        o = fma(gp[i].x, gp[i].x, fma(gp[i].y, gp[i].y, o));
+        d.x = fma(g[i].x, gp[i].x, fma(g[i].y, gp[i].y, d.x));   // conj(g) * gp
+        d.y = fma(g[i].x, gp[i].y, d.y);
+        dyb = fma(g[i].y, gp[i].x, dyb);
     }
-    const double dd = zabs2(d);
-    if (dd > tol2 * m * o && dd > floor2) {
+    d.y -= dyb;
+    const double dd = fma(d.x, d.x, d.y * d.y);
+    if (dd > tol2 * (m * o) && dd > floor2) {
         const double absd = sqrt(dd);
         const double sigma = (j < p) ? 1.0 : -1.0;
         const double zeta = sigma * (o - m) / (2.0 * absd);
@@ -167,17 +178,17 @@ SD void herm_matvec(const cd (&col)[C], const cd (&x)[C], cd (&y)[C]) {
     for (int i = 0; i < C; ++i) y[i] = zshfl<Grp<C>::W>(mine, i);
 }
 
-// ---- the same sweeps in float32, polished in float64 --------------------------------------
-// What the reference computes with LAPACK's SINGLE precision cheevd (solve_pevd on complex64,
-// libs/beamformer.py:40-46) does not need 13 000 fp64 instructions per wavefront: the sweeps
-// run on a float32 copy of the matrix (scaled to max diag = 1), whose rotations are half the
+// ---- the same sweeps in float32, refined in float64 ----------------------------------------
+// 13 000 fp64 instructions per wavefront are not needed for a float32 answer: the sweeps run on
+// a float32 copy of the matrix (scaled to max diag = 1), whose rotations are half the
 // instructions (the partner column arrives through the DPP operand of the fused multiply-adds
-// themselves, no separate moves of 64-bit halves) at twice the issue rate; the principal
-// column they find is then polished against the float64 matrix by two power steps (each
-// multiplies the error components by lambda_i / lambda_1 <= 1: it can only help) and its
-// eigenvalue is the float64 Rayleigh norm.  One-sided Jacobi is backward stable in its working
-// precision, so before the polish the vector is what LAPACK's float32 solver would give; after
-// it, bins with a clear gap are float64-accurate.
+// themselves, no separate moves of 64-bit halves) at twice the issue rate.  What they deliver by
+// themselves is NOT what a float32 LAPACK would give: they stop at a cosine of 1e-6 .. 3e-6
+// between columns, which an eigenvalue gap turns into an error of cosine / (2 gap) -- measured
+// 50 (gap 1e-2) to 7000 (gap 1e-3) times the reference's own sensitivity when only power steps
+// followed.  The refinement in pevd_mixed (a first-order correction in the basis of the columns,
+// against the float64 matrix) removes that: after it the vector is float64-accurate at every
+// gap the tests construct (error 2.5e-8 = the rounding of the float32 output).
 template <int M>
 SD float fxor(float x) {
     return __builtin_bit_cast(float, dpp_xor<M>(__builtin_bit_cast(int, x)));
@@ -185,8 +196,8 @@ SD float fxor(float x) {
 // floor2: columns far below the principal one carry its rounding noise (eps32 |g_max| per
 // entry), so their inner products with it never fall under the RELATIVE bound; below
 // ~eps32 |g_max|^2 an inner product is noise and rotating on it would go on forever (de Rijk's
-// threshold).  What is left un-annihilated there moves the principal vector by ~1e-6 at most,
-// and the float64 power steps shrink exactly those components by lambda_small / lambda_max.
+// threshold).  What is left un-annihilated there is removed by the float64 refinement of
+// pevd_mixed.
 template <int C, int M>
 SD bool jacobi_round_f32(float2 (&g)[C], int j, float floor2) {
     const float tol2 = 1e-11f;  // |g_p^H g_q|^2 <= tol2 |g_p|^2 |g_q|^2: the float32 noise floor is ~1e-13
@@ -194,16 +205,25 @@ SD bool jacobi_round_f32(float2 (&g)[C], int j, float floor2) {
     float2 gp[C];
     float m = 0.f;
     float2 d = make_float2(0.f, 0.f);
+    float dyb = 0.f;
+    // Both lanes of the pair must take the SAME decision from the SAME numbers, or one column
+    // rotates and the other does not and G stops being A times a unitary matrix (seen as a
+    // principal vector 29 degrees off on one matrix in a hundred at a 0.1 % gap, status OK).
+    // So every sum is formed so that the partner gets it bit for bit: d.x is symmetric in (g, gp)
+    // as written; d.y = sum g.x gp.y - sum g.y gp.x in two chains, which the partner computes
+    // swapped and therefore negated exactly; and the bound is tol2 * (m * o).
 #pragma unroll
     for (int i = 0; i < C; ++i) {
         gp[i] = make_float2(fxor<M>(g[i].x), fxor<M>(g[i].y));
         m = fmaf(g[i].x, g[i].x, fmaf(g[i].y, g[i].y, m));
         d.x = fmaf(g[i].x, gp[i].x, fmaf(g[i].y, gp[i].y, d.x));   // conj(g) * gp
-        d.y = fmaf(g[i].x, gp[i].y, fmaf(-g[i].y, gp[i].x, d.y));
+        d.y = fmaf(g[i].x, gp[i].y, d.y);
+        dyb = fmaf(g[i].y, gp[i].x, dyb);
     }
+    d.y -= dyb;
     const float o = fxor<M>(m);
     const float dd = fmaf(d.x, d.x, d.y * d.y);
-    if (dd > tol2 * m * o && dd > floor2) {
+    if (dd > tol2 * (m * o) && dd > floor2) {
         const float rabs = __builtin_amdgcn_rsqf(dd);
         const float sigma = (j < p) ? 1.f : -1.f;
         const float zeta = sigma * (o - m) * 0.5f * rabs;
@@ -291,20 +311,64 @@ SD void pevd_mixed(const cd (&a)[C], int j, cd (&out)[C], double& lam, int& noco
         double inv = (nn > 0.0) ? 1.0 / sqrt(nn) : 0.0;
 #pragma unroll
         for (int i = 0; i < C; ++i) v[i] = zscale(v[i], inv);
-        // two power steps against the float64 matrix; the last norm is the eigenvalue
-        lam = 0.0;
+        // Refinement against the float64 matrix.  The sweeps stop with a cosine of up to 1e-6
+        // between two columns (floor2 / tol2), which an eigenvalue gap `gap` turns into an error
+        // of cosine / (2 gap) in the vector: 3e-3 at a 0.1 % gap, and power steps gain nothing
+        // there.  But every lane still holds its own column g_j = A v_j, i.e. an approximate
+        // eigenvector u_j = g_j / |g_j| with eigenvalue |g_j| (times the scaling dg): in that basis
+        // (theta - A)^-1 is diagonal to first order, so the residual r = A v - theta v of the
+        // principal vector is corrected by  v += sum_j u_j (u_j^H r) / (theta - theta_j)  -- one
+        // step of first-order perturbation theory, whose own error is (cosine / gap) times the
+        // correction, whatever the gap.  Two such steps, then one power step: on a rank-deficient
+        // matrix the null-space columns are rounding noise, not eigenvectors, and what they add
+        // (at most |r| / theta) lies in the null space, which the power step removes exactly.
+        const double nj = sqrt((double)m);             // |g_j|: own column
+        const double ij = (nj > 0.0) ? 1.0 / nj : 0.0;
+        const double theta_j = nj * dg;
+        cd y[C];
 #pragma unroll 1
         for (int it = 0; it < 2; ++it) {
-            cd y[C];
             herm_matvec<C>(a, v, y);
+            double theta = 0.0;
+#pragma unroll
+            for (int i = 0; i < C; ++i) theta += zcmul(v[i], y[i]).x;
+            cd c = make_double2(0.0, 0.0);                 // u_j^H r
+#pragma unroll
+            for (int i = 0; i < C; ++i) {
+                const cd u = make_double2((double)g[i].x * ij, (double)g[i].y * ij);
+                c = zadd(c, zcmul(u, zsub(y[i], zscale(v[i], theta))));
+            }
+            // (theta_j carries the float32 rounding of the column: a difference below 16 eps32
+            //  theta is noise -- an exactly or nearly multiple eigenvalue, where any vector of the
+            //  invariant subspace is an answer)
+            const double den = theta - theta_j;
+            const bool use = j != bj && nj > 0.0 && fabs(den) > 16.0 * kEpsF32 * fabs(theta);
+            const cd coef = use ? zscale(c, 1.0 / den) : make_double2(0.0, 0.0);
             nn = 0.0;
 #pragma unroll
-            for (int i = 0; i < C; ++i) nn += zabs2(y[i]);
-            lam = sqrt(nn);
-            inv = (lam > 0.0) ? 1.0 / lam : 0.0;
+            for (int i = 0; i < C; ++i) {
+                cd t = zmul(make_double2((double)g[i].x * ij, (double)g[i].y * ij), coef);
 #pragma unroll
-            for (int i = 0; i < C; ++i) v[i] = zscale(y[i], inv);
+                for (int sft = 1; sft < W; sft <<= 1) {
+                    t.x += __shfl_xor(t.x, sft, W);
+                    t.y += __shfl_xor(t.y, sft, W);
+                }
+                v[i] = zadd(v[i], t);
+                nn += zabs2(v[i]);
+            }
+            inv = (nn > 0.0) ? 1.0 / sqrt(nn) : 0.0;
+#pragma unroll
+            for (int i = 0; i < C; ++i) v[i] = zscale(v[i], inv);
         }
+        // the power step; its norm is the eigenvalue
+        herm_matvec<C>(a, v, y);
+        nn = 0.0;
+#pragma unroll
+        for (int i = 0; i < C; ++i) nn += zabs2(y[i]);
+        lam = sqrt(nn);
+        inv = (lam > 0.0) ? 1.0 / lam : 0.0;
+#pragma unroll
+        for (int i = 0; i < C; ++i) v[i] = zscale(y[i], inv);
 #pragma unroll
         for (int i = 0; i < C; ++i) {
             out[i] = v[i];
@@ -701,7 +765,7 @@ __global__ __launch_bounds__(64, (C > 8) ? 1 : 2) void solve_kernel(SolveArgs a,
                 }
             }
             __syncthreads();
-            double ps = 0.0, pn = 0.0;
+            double ps = 0.0, pn = 0.0, nb = 0.0;
 #pragma unroll
             for (int i = 0; i < C; ++i) {
                 cd s1 = make_double2(0.0, 0.0), s2 = s1;
@@ -712,7 +776,12 @@ __global__ __launch_bounds__(64, (C > 8) ? 1 : 2) void solve_kernel(SolveArgs a,
                 }
                 ps += zcmul(x[i], s1).x;
                 pn += zcmul(x[i], s2).x;
+                nb += zabs2(s2);
             }
+            // do_ban of this candidate, here where the weight and Rn w are still float64: from
+            // the float32 copy in wmat |Rn w| loses eps32 * cond(Rn) (3.7e-4 at cond 1e5).  The
+            // SNR terms are those of the unnormalised weight, as in the reference.
+            const double filt = (a.flags & SETK_FLAG_BAN) ? sqrt(nb) / fmax(pn, kEpsF32) : 1.0;
             if (live && j < C) {
                 // per-bin terms; pmwf_select_kernel sums them in bin order (an atomic
                 // accumulation would make the argmax depend on the arrival order)
@@ -720,7 +789,7 @@ __global__ __launch_bounds__(64, (C > 8) ? 1 : 2) void solve_kernel(SolveArgs a,
                 a.snr_acc[((size_t)prob * C + j) * 2 + 1] = pn;
                 float2* wm = reinterpret_cast<float2*>(a.wmat) + ((size_t)prob * C + j) * C;
 #pragma unroll
-                for (int i = 0; i < C; ++i) wm[i] = make_float2((float)x[i].x, (float)x[i].y);
+                for (int i = 0; i < C; ++i) wm[i] = make_float2((float)(x[i].x * filt), (float)(x[i].y * filt));
             }
         }
     }
@@ -752,7 +821,14 @@ __global__ __launch_bounds__(64, (C > 8) ? 1 : 2) void solve_kernel(SolveArgs a,
     bool wfin = true;
 #pragma unroll
     for (int i = 0; i < C; ++i) wfin = wfin && isfinite(w[i].x) && isfinite(w[i].y);
-    if (!__all(finite) || !wfin) st = (st == SETK_NUM_OK) ? SETK_NUM_NONFINITE : st;
+    // the vote is over the lanes of THIS problem (each checked its own column): a wavefront
+    // holds 4 / 8 / 16 problems and a NaN bin must not mark its healthy neighbours
+    int fin = finite ? 1 : 0;
+#pragma unroll
+    for (int sft = 1; sft < W; sft <<= 1) fin &= __shfl_xor(fin, sft, W);
+    // a NaN / inf in the input is reported as such, whatever the factorisation made of it (a NaN
+    // pivot also raises SINGULAR); a non-finite RESULT of finite input only where nothing else was
+    if (!fin || (!wfin && st == SETK_NUM_OK)) st = SETK_NUM_NONFINITE;
     if (live) {
         if (j < C && !(kind == SETK_BF_PMWF && a.pmwf_ref < 0)) {
             cd wj = make_double2(0.0, 0.0);
@@ -970,13 +1046,13 @@ hipError_t launch_solve(const SolveArgs& a, hipStream_t s) {
 
 // ---------------------------------------------------------------------------
 // PMWF with SNR-selected reference channel: pick argmax_c ps/max(eps, pn) per
-// utterance (libs/beamformer.py:650-653), copy that column out, optional BAN.
+// utterance (libs/beamformer.py:650-653), copy that column out (solve_kernel has applied
+// the optional BAN to every candidate column in float64 already).
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void pmwf_select_kernel(SolveArgs a, int pitch, int* ref_out) {
     const int u = blockIdx.y;
     const int f = blockIdx.x * 256 + threadIdx.x;
     const int C = a.num_channels, F = a.num_bins;
-    const int NP = npairs(C);
     // sum_f of the per-bin (ps, pn) terms in a fixed order: thread c sums channel c
     __shared__ double s_snr[kMaxChannels16][2];
     if (threadIdx.x < C) {
@@ -1004,34 +1080,9 @@ __global__ __launch_bounds__(256) void pmwf_select_kernel(SolveArgs a, int pitch
     if (f >= F) return;
     const size_t prob = (size_t)u * F + f;
     const float2* wm = reinterpret_cast<const float2*>(a.wmat) + (prob * C + ref) * C;
-    double2 w[kMaxChannels16];
-    for (int i = 0; i < C; ++i) w[i] = make_double2(wm[i].x, wm[i].y);
-    if (a.flags & SETK_FLAG_BAN) {
-        const float* base = a.covar + (size_t)u * a.planes * pitch + f;
-        double nom = 0.0, den = 0.0;
-        for (int i = 0; i < C; ++i) {
-            double2 ui = make_double2(0.0, 0.0);
-            for (int m = 0; m < C; ++m) {
-                const int lo = i < m ? i : m, hi = i < m ? m : i;
-                const int e = pair_index(lo, hi, C);
-                const double re = base[(size_t)(2 * NP + e) * pitch];
-                double im = (i == m) ? 0.0 : base[(size_t)(3 * NP + e) * pitch];
-                if (i > m) im = -im;  // Rn[i][m] = conj(Rn[m][i])
-                ui.x += re * w[m].x - im * w[m].y;
-                ui.y += re * w[m].y + im * w[m].x;
-            }
-            nom += ui.x * ui.x + ui.y * ui.y;
-            den += w[i].x * ui.x + w[i].y * ui.y;
-        }
-        const double filt = sqrt(nom) / fmax(den, kEpsF32);
-        for (int i = 0; i < C; ++i) {
-            w[i].x *= filt;
-            w[i].y *= filt;
-        }
-    }
     for (int i = 0; i < C; ++i) {
         float2* dst = reinterpret_cast<float2*>(a.weight) + ((size_t)u * C + i) * pitch + f;
-        *dst = make_float2((float)w[i].x, (float)w[i].y);
+        *dst = wm[i];
     }
 }
 
@@ -1046,14 +1097,24 @@ hipError_t launch_pmwf_select(const SolveArgs& a, int* ref_out, hipStream_t s) {
 // layout helpers for the modular API
 // ---------------------------------------------------------------------------
 // covar[F][C][C] complex64 -> packed planes [2*NP][pitch] starting at plane0
-// Cp >= C: the matrix is embedded in a Cp x Cp one, blkdiag(M, pad_diag * I): with
-// pad_diag = 1 for the matrices that get factored (Rn, Ry) and 0 for Rs the padded
-// problem has the original's solution in its first C components and zeros after.
+// Cp >= C: the matrix is embedded in a Cp x Cp one, blkdiag(M, pad * I), pad = pad_diag *
+// max_i Re M[i][i] of that bin: with pad_diag = 1 for the matrices that get factored (Rn, Ry)
+// and 0 for Rs the padded problem has the original's solution in its first C components and
+// zeros after.  The pad follows the matrix so that chol_lds sees the same `max diag` as on the
+// C x C problem: its pivot floor, its refusal of an all-zero / negative-diagonal matrix and the
+// strict-reference identity branch then do not depend on the embedding (a constant 1 floored
+// every real pivot of a covariance below 1.2e-7 and hid an all-zero Rn; tests/chol_model.py).
 __global__ void pack_covar_kernel(const float2* fcc, int F, int C, int Cp, float pad_diag,
                                   int pitch, float* planes, int plane0) {
     const int f = blockIdx.x * 256 + threadIdx.x;
     if (f >= pitch) return;
     const int NP = npairs(Cp);
+    float pad = 0.f;
+    if (f < F && Cp > C && pad_diag != 0.f) {
+        float dmax = fcc[(size_t)f * C * C].x;
+        for (int i = 1; i < C; ++i) dmax = fmaxf(dmax, fcc[((size_t)f * C + i) * C + i].x);
+        pad = pad_diag * dmax;
+    }
     for (int i = 0; i < Cp; ++i)
         for (int j = i; j < Cp; ++j) {
             const int e = pair_index(i, j, Cp);
@@ -1067,7 +1128,7 @@ __global__ void pack_covar_kernel(const float2* fcc, int F, int C, int Cp, float
                     const float2 l = fcc[((size_t)f * C + j) * C + i];
                     v = make_float2(l.x, i == j ? 0.f : -l.y);
                 } else if (i == j) {
-                    v = make_float2(pad_diag, 0.f);
+                    v = make_float2(pad, 0.f);
                 }
             }
             planes[(size_t)(plane0 + e) * pitch + f] = v.x;

@@ -639,3 +639,28 @@ def test_float_samples_beyond_unit_range(ctx, kind, scale):
     assert rms(ys / scale, y1) / rms(y1) < 1e-4  # (a scale that is no power of two moves roundings)
     ref = o.enhance_utterance(mix * np.float32(scale), mask, kind=kind, gauge=True)
     assert rms(ys, ref) / rms(ref) < 1e-3
+
+
+@pytest.mark.parametrize("C", [8, 4])
+@pytest.mark.parametrize("value", [np.nan, np.inf])
+def test_a_nonfinite_utterance_does_not_mark_its_neighbours(ctx, C, value):
+    """The per-utterance status is the worst of its own 257 bins.  Bins of three utterances share
+    wavefronts of the solve (257 is no multiple of the 8 / 16 problems a wavefront holds), so one
+    NaN or inf sample in the middle utterance must report SETK_NUM_NONFINITE there and leave the
+    outer two alone: status 0 and the waveform of the same batch with a clean middle utterance,
+    bit for bit (the streaming CLI drops every wav whose status is not 0)."""
+    from setk_amd import _ffi
+    utts, masks = [], []
+    for i in range(3):
+        mix, sp, nz = o.synth_utterance(70 + i, C, 12000, return_parts=True)
+        utts.append(mix)
+        masks.append(o.irm_mask(sp, nz))
+    opts = lambda: _ffi.BfOpts(flags=_ffi.FLAG_CLAMP_MASK, **KINDS["mvdr"])  # noqa: E731
+    clean, st = run_batch(ctx, opts(), utts, masks)
+    assert st == [0, 0, 0]
+    bad = [u.copy() for u in utts]
+    bad[1][C // 2, 5000] = value
+    got, st = run_batch(ctx, opts(), bad, masks)
+    assert st == [0, _ffi.NUM_NONFINITE, 0], st
+    for k in (0, 2):
+        assert np.array_equal(got[k].view(np.uint32), clean[k].view(np.uint32)), k
