@@ -435,6 +435,41 @@ int setk_wpe_batch_fnt(setk_handle_t h, int n_utts, const float* const* spec, in
                        const int* num_frames, int num_bins, int taps, int delay, int context,
                        int num_iters, float* const* out, int* status, void* stream);
 
+/* ---- AuxIVA blind source separation (scripts/sptk/apply_auxiva.py) ----------
+ * auxiva(X, epochs) (:24-57): as many sources as channels, demixing matrices W_f = I to start
+ * with; per epoch r_n(t) = sqrt(sum_f |y_n(f, t)|^2), g = 1 / (r + float32 eps) (:42-44), per bin
+ * and source in order V_n = sum_t g_n x x^H / T, w = solve(W^H V_n, e_n), W[:, n] = w / (w^H V_n w)
+ * (:45-52), y = W^H x (:54).  Observations are complex64 like the reference's; g, V, W, the
+ * solves, y and r are float64 (the reference's complex128 -- in float32 the doc recording
+ * deviates by 5e-4).  Two runs on the same input give the same bits (no floating-point atomics).
+ *   spec / out  [C][T][F] complex64, host or device: the reference's N x T x F.  Any F, any T.
+ *               num_epochs = 0 returns spec (Y = X conj(I)).
+ *   status      [F] or NULL, host or device: SETK_NUM_SINGULAR where a pivot of the LU with
+ *               partial pivoting of some W^H V_n was exactly zero (a silent channel, an all-zero
+ *               utterance: numpy.linalg.solve raises LinAlgError("Singular matrix") there, :51,
+ *               and the reference's run ends), SETK_NUM_NONFINITE for NaN / inf in the bin's
+ *               input or result; worst over epochs and sources.  The output of such a bin is
+ *               not meaningful.
+ * SETK_ERR_UNSUPPORTED: num_channels outside 1 .. 8. */
+int setk_auxiva(setk_handle_t h, const float* spec, int num_channels, int num_frames, int num_bins,
+                int num_epochs, float* out, int* status, void* stream);
+
+/* The loop body of run() (apply_auxiva.py:60-79) for a batch of utterances with the same channel
+ * count: STFT straight into the bin-major layout of the epoch kernels, the epochs, the
+ * inverse STFT of every source, renorm to max |audio[u]| (inverse_stft(norm=maxabs), :74-76).
+ *   audio[u]   device float32 [C][num_samples[u]]
+ *   wave[u]    device float32 [C][L_u], L_u = setk_istft_num_samples(T_u, -1) (hop (T_u - 1) when
+ *              centred); with SETK_FLAG_OUT_PCM16 int16 [C][L_u] (libsndfile's float -> PCM_16)
+ *   status[u]  worst bin status of the utterance, host or device, or NULL
+ * The pointer tables and num_samples are HOST arrays of n_utts entries.  Requires the
+ * n_fft = 512 plan and 1 <= C <= 8; scratch comes from the handle's arena; the call returns
+ * when the work has run.  With setk_set_profiling the stage times of setk_last_stage_ms are
+ * out[0] STFT + max |audio|, out[1] the epochs (with their projections), out[2] transposition
+ * + inverse STFT, out[3] renorm. */
+int setk_auxiva_batch(setk_handle_t h, int n_utts, int num_channels, const float* const* audio,
+                      const int* num_samples, int num_epochs, void* const* wave, int* status,
+                      int flags, void* stream);
+
 /* ---- fused hot path ------------------------------------------------------
  * The compute body of apply_adaptive_beamformer.py:130-178 for a batch of
  * utterances that share the channel count, in four kernel stages:

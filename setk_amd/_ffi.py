@@ -113,7 +113,7 @@ def exported_symbols():
         "setk_pcm16_to_float", "setk_pcm16_to_float_batch", "setk_pcm16_channel_stride", "setk_pcm16_deinterleave_batch", "setk_kaldi_cm_decode_batch", "setk_float_to_pcm16", "setk_ban", "setk_rank1", "setk_beamform", "setk_cgmm_masks", "setk_cgmm_masks_k", "setk_cgmm_masks_k_status",
         "setk_cgmm_masks_batch", "setk_cgmm_estimate_batch", "setk_enhance_batch", "setk_enhance_batch_taps",
         "setk_apply_weights_batch",
-        "setk_directional_feats", "setk_wpe", "setk_wpe_step", "setk_wpe_batch", "setk_wpe_batch_fnt", "setk_wpe_batch_var", "setk_set_profiling",
+        "setk_directional_feats", "setk_wpe", "setk_wpe_step", "setk_wpe_batch", "setk_wpe_batch_fnt", "setk_wpe_batch_var", "setk_auxiva", "setk_auxiva_batch", "setk_set_profiling",
         "setk_last_stage_ms",
         "setk_comm_unique_id", "setk_comm_create", "setk_comm_allreduce_f64", "setk_comm_barrier",
         "setk_comm_destroy", "setk_comm_last_error", "setk_host_read_payloads"
@@ -217,6 +217,9 @@ def load_library():
     lib.setk_wpe_batch_var.argtypes = [H, c_int, POINTER(c_void_p), c_int, POINTER(c_int), c_int, c_int,
                                        c_int, c_int, c_int, POINTER(c_void_p), POINTER(c_void_p),
                                        POINTER(c_void_p), fp, c_void_p]
+    lib.setk_auxiva.argtypes = [H, fp, c_int, c_int, c_int, c_int, fp, fp, c_void_p]
+    lib.setk_auxiva_batch.argtypes = [H, c_int, c_int, POINTER(c_void_p), POINTER(c_int), c_int,
+                                      POINTER(c_void_p), fp, c_int, c_void_p]
     lib.setk_directional_feats.argtypes = [H, fp, fp, POINTER(c_int), c_int, c_int, c_int, c_int,
                                            fp, c_void_p]
     lib.setk_apply_weights_batch.argtypes = [
@@ -697,6 +700,27 @@ class Context:
             self._lib.setk_wpe_step(self._h, _ptr(spec), int(C), int(T), int(F), int(taps), int(delay),
                                     _ptr(lambda_ft), _ptr(out), _ptr(status),
                                     current_stream_ptr() if stream is None else stream))
+
+    def auxiva(self, spec, C, T, F, num_epochs, out, status=None, stream=None):
+        """auxiva() of apply_auxiva.py:24-57: spec / out [C][T][F] complex64 (numpy or device
+        tensors); status int32[F] (numpy or device address) or None: SETK_NUM_* per bin."""
+        self.check(
+            self._lib.setk_auxiva(self._h, _ptr(spec), int(C), int(T), int(F), int(num_epochs),
+                                  _ptr(out), _ptr(status),
+                                  current_stream_ptr() if stream is None else stream))
+
+    def auxiva_batch(self, C, audio_ptrs, num_samples, num_epochs, wave_ptrs, status=None, flags=0,
+                     stream=None):
+        """Audio in, separated waves out (device addresses): wave[u] is [C][L_u] float32, or
+        int16 with FLAG_OUT_PCM16; status int32[n] (numpy or device address) or None: the worst
+        bin of every utterance."""
+        n = len(audio_ptrs)
+        A = (c_void_p * n)(*audio_ptrs)
+        W = (c_void_p * n)(*wave_ptrs)
+        NS = (c_int * n)(*[int(v) for v in num_samples])
+        self.check(
+            self._lib.setk_auxiva_batch(self._h, n, int(C), A, NS, int(num_epochs), W, _ptr(status),
+                                        int(flags), current_stream_ptr() if stream is None else stream))
 
     def set_profiling(self, on):
         self.check(self._lib.setk_set_profiling(self._h, 1 if on else 0))

@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libsetk_hip.so")
-SOURCES = ["pass1.hip", "pass1_mc.hip", "pass2.hip", "pass2_mc.hip", "solve.hip", "modular.hip", "cgmm.hip", "cgmm_bin.hip", "cgmm_k.hip", "wpe.hip", "comm.hip", "hostio.hip", "capi.hip"]
+SOURCES = ["pass1.hip", "pass1_mc.hip", "pass2.hip", "pass2_mc.hip", "solve.hip", "modular.hip", "cgmm.hip", "cgmm_bin.hip", "cgmm_k.hip", "wpe.hip", "auxiva.hip", "comm.hip", "hostio.hip", "capi.hip"]
 HEADERS = ["common.h", "fft512.h", "dpp.h", "covar_fold.h", "mcdft.h", "mcdft_tables.h", os.path.join("..", "..", "include", "setk_hip.h")]
 ARCH = "gfx950"
 
@@ -67,6 +67,7 @@ def _build_locked(force, verbose):
              "cgmm_bin.hip": ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"],
              "cgmm_k.hip": [],
              "wpe.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"],
+             "auxiva.hip": [],
              "comm.hip": [],
              "capi.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]}
     # solve.hip and modular.hip hold a kernel each that must round like numpy operation by operation

@@ -2278,4 +2278,246 @@ int setk_enhance_batch_taps(setk_handle_t h, const setk_bf_opts* opts, int n_utt
     return SETK_OK;
 }
 
+namespace {
+struct AuxUtt {
+    const float* x_bin;  // [F][C][Tp] complex64 (device)
+    int T, Tp;
+    double* pw;          // [F][C][Tp] float64: |y|^2 between the epochs, y (complex64) at the end
+};
+
+// auxiva() (apply_auxiva.py:24-57) on observations that lie bin-major on the device: the epoch-0
+// powers, then per epoch one norm launch and one epoch launch over every (bin, utterance).
+// Leaves y as complex64 [F][C][Tp] in us[u].pw and the per-bin status in d_st [n_utts][F].
+int auxiva_run(setk_handle_t h, int C, int F, int num_epochs, std::vector<AuxUtt>& us, int** d_st_out,
+               hipStream_t s) {
+    const int n_utts = (int)us.size();
+    int* d_st = static_cast<int*>(arena_alloc(h, (size_t)n_utts * F * sizeof(int)));
+    if (!d_st) return fail(h, SETK_ERR_NOMEM, "arena");
+    HIP_TRY(h, hipMemsetAsync(d_st, 0, (size_t)n_utts * F * sizeof(int), s));
+    const size_t ab = auxiva_args_bytes();
+    std::vector<char> tbl((size_t)n_utts * ab);
+    int max_frames = 0;
+    for (int u = 0; u < n_utts; ++u) {
+        AuxUtt& q = us[u];
+        max_frames = std::max(max_frames, q.T);
+        q.pw = static_cast<double*>(arena_alloc(h, (size_t)F * C * q.Tp * sizeof(double)));
+        double* g = static_cast<double*>(arena_alloc(h, (size_t)C * q.Tp * sizeof(double)));
+        void* W = arena_alloc(h, (size_t)F * C * C * 2 * sizeof(double));
+        if (!q.pw || !g || !W) return fail(h, SETK_ERR_NOMEM, "arena");
+        auxiva_fill_args(tbl.data() + (size_t)u * ab, q.x_bin, q.pw, g, W, d_st + (size_t)u * F, q.T,
+                         q.Tp);
+    }
+    void* d_tbl;
+    int rc = upload(h, tbl.data(), tbl.size(), s, &d_tbl);
+    if (rc) return rc;
+    HIP_TRY(h, launch_auxiva_epoch(d_tbl, n_utts, C, F, false, num_epochs == 0, s));
+    for (int e = 1; e <= num_epochs; ++e) {
+        HIP_TRY(h, launch_auxiva_norm(d_tbl, n_utts, C, F, max_frames, s));
+        HIP_TRY(h, launch_auxiva_epoch(d_tbl, n_utts, C, F, true, e == num_epochs, s));
+    }
+    *d_st_out = d_st;
+    return SETK_OK;
+}
+}  // namespace
+
+int setk_auxiva(setk_handle_t h, const float* spec, int num_channels, int num_frames, int num_bins,
+                int num_epochs, float* out, int* status, void* stream) {
+    if (!h || !spec || !out || num_frames <= 0 || num_bins <= 0 || num_epochs < 0)
+        return fail(h, SETK_ERR_INVALID, "bad args");
+    const int C = num_channels, T = num_frames, F = num_bins;
+    if (!auxiva_supported(C)) return fail(h, SETK_ERR_UNSUPPORTED, auxiva_limit_message());
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    HIP_TRY(h, hipSetDevice(h->device));
+    arena_reset(h, s);
+    const size_t n = (size_t)C * T * F;
+    const float* d_spec;
+    int rc = stage_in(h, spec, n * 2, s, &d_spec);
+    if (rc) return rc;
+    OutBuf ob;
+    rc = stage_out(h, out, n * sizeof(float2), &ob);
+    if (rc) return rc;
+    std::vector<AuxUtt> us(1);
+    us[0].T = T;
+    us[0].Tp = (T + 3) & ~3;
+    float* xb = static_cast<float*>(arena_alloc(h, (size_t)F * C * us[0].Tp * sizeof(float2)));
+    if (!xb) return fail(h, SETK_ERR_NOMEM, "arena");
+    us[0].x_bin = xb;
+    HIP_TRY(h, launch_auxiva_transpose(d_spec, C, T, F, us[0].Tp, xb, true, s));
+    int* d_st = nullptr;
+    rc = auxiva_run(h, C, F, num_epochs, us, &d_st, s);
+    if (rc) return rc;
+    HIP_TRY(h, launch_auxiva_transpose(reinterpret_cast<const float*>(us[0].pw), C, T, F, us[0].Tp,
+                                       static_cast<float*>(ob.dev), false, s));
+    rc = copy_back(h, ob, s);
+    if (rc) return rc;
+    if (status)
+        HIP_TRY(h, hipMemcpyAsync(status, d_st, (size_t)F * sizeof(int),
+                                  is_device_ptr(status) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
+                                  s));
+    // staged buffers and scratch live in the arena: drained before the next call reuses it
+    HIP_TRY(h, hipStreamSynchronize(s));
+    return SETK_OK;
+}
+
+int setk_auxiva_batch(setk_handle_t h, int n_utts, int num_channels, const float* const* audio,
+                      const int* num_samples, int num_epochs, void* const* wave, int* status,
+                      int flags, void* stream) {
+    if (!h || n_utts <= 0 || !audio || !num_samples || !wave || num_epochs < 0)
+        return fail(h, SETK_ERR_INVALID, "bad args");
+    int rc = require_plan512(h);
+    if (rc) return rc;
+    const int C = num_channels, F = kBins;
+    if (!auxiva_supported(C)) return fail(h, SETK_ERR_UNSUPPORTED, auxiva_limit_message());
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    HIP_TRY(h, hipSetDevice(h->device));
+    arena_reset(h, s);
+    const bool pcm16 = (flags & SETK_FLAG_OUT_PCM16) != 0;
+
+    const bool prof = h->profiling;
+    if (prof) {
+        for (int i = 0; i < 5; ++i) {
+            hipEvent_t e;
+            if (!h->ev_pool.empty()) {
+                e = h->ev_pool.back();
+                h->ev_pool.pop_back();
+            } else {
+                HIP_TRY(h, hipEventCreate(&e));
+            }
+            h->ev[i] = e;
+            h->ev_used.push_back(e);
+        }
+        HIP_TRY(h, hipEventRecord(h->ev[0], s));
+    }
+
+    // ---- STFT of every utterance straight into the bin-major layout; max |audio| ----
+    std::vector<AuxUtt> us(n_utts);
+    std::vector<UttDesc> uds(n_utts);
+    std::vector<WorkItem> items;
+    int max_samples = 0;
+    for (int u = 0; u < n_utts; ++u) {
+        if (!audio[u] || !wave[u]) return fail(h, SETK_ERR_INVALID, "null utterance pointer");
+        if (!is_device_ptr(audio[u]) || !is_device_ptr(wave[u]))
+            return fail(h, SETK_ERR_INVALID, "setk_auxiva_batch takes device pointers");
+        const int T = setk_stft_num_frames(h, num_samples[u]);
+        if (T <= 0) return T < 0 ? T : fail(h, SETK_ERR_INVALID, "utterance shorter than a frame");
+        us[u].T = T;
+        us[u].Tp = (T + 3) & ~3;
+        float* xb = static_cast<float*>(arena_alloc(h, (size_t)F * C * us[u].Tp * sizeof(float2)));
+        if (!xb) return fail(h, SETK_ERR_NOMEM, "arena");
+        us[u].x_bin = xb;
+        UttDesc& ud = uds[u];
+        memset(&ud, 0, sizeof(ud));
+        ud.audio = audio[u];
+        ud.num_samples = num_samples[u];
+        ud.num_frames = T;
+        ud.wave_out = xb;
+        max_samples = std::max(max_samples, num_samples[u]);
+        for (int t0 = 0; t0 < T; t0 += 64) items.push_back({u, t0, std::min(t0 + 64, T), 0, t0 + 64 >= T});
+    }
+    void *d_ud, *d_items;
+    rc = upload(h, uds.data(), uds.size() * sizeof(UttDesc), s, &d_ud);
+    if (rc) return rc;
+    rc = upload(h, items.data(), items.size() * sizeof(WorkItem), s, &d_items);
+    if (rc) return rc;
+    const int n_src = n_utts * C;
+    // [n_utts] max |audio| | [n_src] the same per source | [n_src] max |source wave|
+    unsigned* d_norm = static_cast<unsigned*>(arena_alloc(h, (size_t)(n_utts + 2 * n_src) * sizeof(unsigned)));
+    if (!d_norm) return fail(h, SETK_ERR_NOMEM, "arena");
+    unsigned* d_norm_src = d_norm + n_utts;
+    unsigned* d_omax = d_norm_src + n_src;
+    HIP_TRY(h, hipMemsetAsync(d_norm, 0, (size_t)(n_utts + 2 * n_src) * sizeof(unsigned), s));
+    {
+        Pass1Args a;
+        memset(&a, 0, sizeof(a));
+        a.utts = static_cast<const UttDesc*>(d_ud);
+        a.items = static_cast<const WorkItem*>(d_items);
+        a.window = h->d_window;
+        a.tw256 = h->d_tw256;
+        a.tw512 = h->d_tw512;
+        a.g = geom_of(h);
+        HIP_TRY(h, launch_stft_binmajor(C, a, (int)items.size(), s));
+        // SpectrogramReader.maxabs(key), the norm of inverse_stft (apply_auxiva.py:74-76)
+        HIP_TRY(h, launch_maxabs(a.utts, C, d_norm, n_utts, max_samples, s));
+        HIP_TRY(h, launch_auxiva_spread_norm(d_norm, C, n_src, d_norm_src, s));
+    }
+    if (prof) HIP_TRY(h, hipEventRecord(h->ev[1], s));
+
+    // ---- the epochs ----
+    int* d_st = nullptr;
+    rc = auxiva_run(h, C, F, num_epochs, us, &d_st, s);
+    if (rc) return rc;
+    if (prof) HIP_TRY(h, hipEventRecord(h->ev[2], s));
+
+    // ---- y -> [C][T][F], inverse STFT of every source (one item list for the batch) ----
+    std::vector<UttDesc> sds(n_src);
+    std::vector<WorkItem> sitems;
+    int max_len = 0;
+    for (int u = 0; u < n_utts; ++u) {
+        const int T = us[u].T;
+        const int L = setk_istft_num_samples(h, T, -1);
+        max_len = std::max(max_len, L);
+        float* y = static_cast<float*>(arena_alloc(h, (size_t)C * T * F * sizeof(float2)));
+        float* w32 = pcm16 ? static_cast<float*>(arena_alloc(h, (size_t)C * L * sizeof(float)))
+                           : static_cast<float*>(wave[u]);
+        if (!y || !w32) return fail(h, SETK_ERR_NOMEM, "arena");
+        HIP_TRY(h, launch_auxiva_transpose(reinterpret_cast<const float*>(us[u].pw), C, T, F, us[u].Tp, y,
+                                           false, s));
+        if (L > 0) HIP_TRY(h, hipMemsetAsync(w32, 0, (size_t)C * L * sizeof(float), s));
+        std::vector<std::pair<int, int>> ranges;
+        split_frames(T, 128, kSuperTile, &ranges);
+        for (int c = 0; c < C; ++c) {
+            UttDesc& sd = sds[(size_t)u * C + c];
+            memset(&sd, 0, sizeof(sd));
+            sd.audio = y + (size_t)c * T * F * 2;  // ISTFT mode: per-item spectrogram
+            sd.num_frames = T;
+            sd.out_len = L;
+            sd.wave_f32 = w32 + (size_t)c * L;
+            sd.wave_out = pcm16 ? static_cast<void*>(static_cast<int16_t*>(wave[u]) + (size_t)c * L)
+                                : static_cast<void*>(sd.wave_f32);
+            for (auto& r : ranges) sitems.push_back({u * C + c, r.first, r.second, 0, r.second == T});
+        }
+    }
+    void *d_sd, *d_sitems;
+    rc = upload(h, sds.data(), sds.size() * sizeof(UttDesc), s, &d_sd);
+    if (rc) return rc;
+    rc = upload(h, sitems.data(), sitems.size() * sizeof(WorkItem), s, &d_sitems);
+    if (rc) return rc;
+    Pass2Args p2;
+    memset(&p2, 0, sizeof(p2));
+    p2.utts = static_cast<const UttDesc*>(d_sd);
+    p2.items = static_cast<const WorkItem*>(d_sitems);
+    p2.window = h->d_window;
+    p2.synwin = h->d_window;
+    p2.winsq = h->d_winsq;
+    p2.tw256 = h->d_tw256;
+    p2.tw512 = h->d_tw512;
+    p2.outmax_bits = d_omax;
+    p2.g = geom_of(h);
+    HIP_TRY(h, launch_pass2(1, true, p2, (int)sitems.size(), s));
+    if (prof) HIP_TRY(h, hipEventRecord(h->ev[3], s));
+    ScaleArgs sc;
+    memset(&sc, 0, sizeof(sc));
+    sc.utts = p2.utts;
+    sc.norm_bits = d_norm_src;
+    sc.outmax_bits = d_omax;
+    sc.pcm16 = pcm16 ? 1 : 0;
+    HIP_TRY(h, launch_scale(sc, n_src, max_len, s));
+    if (prof) HIP_TRY(h, hipEventRecord(h->ev[4], s));
+
+    // worst bin of every utterance; the descriptors live in the arena, so the call drains
+    if (status) {
+        std::vector<int> st((size_t)n_utts * F), worst(n_utts, 0);
+        HIP_TRY(h, hipMemcpyAsync(st.data(), d_st, st.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipStreamSynchronize(s));
+        for (int u = 0; u < n_utts; ++u)
+            for (int f = 0; f < F; ++f) worst[u] = std::max(worst[u], st[(size_t)u * F + f]);
+        if (is_device_ptr(status))
+            HIP_TRY(h, hipMemcpy(status, worst.data(), (size_t)n_utts * sizeof(int), hipMemcpyHostToDevice));
+        else
+            memcpy(status, worst.data(), (size_t)n_utts * sizeof(int));
+    }
+    HIP_TRY(h, hipStreamSynchronize(s));
+    return SETK_OK;
+}
+
 }  // extern "C"

@@ -253,4 +253,20 @@ size_t wpe_wide_bytes_per_bin(int N, int taps);
 hipError_t launch_wpe_step_batch(const void* d_tbl, int n_utts, int N, int F, int taps,
                                  hipStream_t s);
 
+// AuxIVA (auxiva.hip): observations [F][C][Tp] complex64, powers [F][C][Tp] float64 (y as
+// complex64 after the last launch), weights [C][Tp] float64, W [F][C][C] complex128
+bool auxiva_supported(int C);
+const char* auxiva_limit_message();
+size_t auxiva_args_bytes();
+void auxiva_fill_args(void* dst, const float* x_bin, double* power, double* g, void* W, int* status,
+                      int T, int Tp);
+hipError_t launch_auxiva_norm(const void* d_tbl, int n_utts, int C, int F, int max_frames,
+                              hipStream_t s);
+hipError_t launch_auxiva_epoch(const void* d_tbl, int n_utts, int C, int F, bool update, bool write_y,
+                               hipStream_t s);
+hipError_t launch_auxiva_transpose(const float* in, int C, int T, int F, int Tp, float* out,
+                                   bool to_bin, hipStream_t s);
+hipError_t launch_auxiva_spread_norm(const unsigned* norm_bits, int C, int n, unsigned* out,
+                                     hipStream_t s);
+
 }  // namespace setk

@@ -14,6 +14,7 @@ import numpy as np
 
 from . import _ffi
 from .libs.utils import nextpow2, stft_window, cmat_abs
+from .libs.wavio import float_to_pcm16 as wavio_float_to_pcm16
 
 BEAMFORMER_KINDS = {
     # name -> (kind, pmwf_beta)
@@ -916,6 +917,106 @@ class BatchDereverb(object):
         host = waves.cpu().numpy()
         return [None if _ffi.wpe_failed(status[u]).any() else host[o:o + C * L].reshape(C, L)
                 for u, (o, L) in enumerate(views)]
+
+
+class BatchSeparator(object):
+    """apply_auxiva.py:60-79 for a batch, resident on the device: the STFT of every channel
+    straight into the bin-major layout, num_epochs AuxIVA epochs over every (bin, utterance)
+    per launch (fp64), the inverse STFT of every source and the renorm to max |input|
+    (setk_auxiva_batch), one upload of the samples and one download of the waveforms per
+    channel count.  run() takes a list of C x N float32 arrays or Pcm16Frames (any mix of
+    channel counts) and returns, per utterance, the C separated sources as a C x L float32
+    array (pcm16: int16, quantised on the device by the writer's rule), or None where a bin was
+    singular or non-finite (the reference's LinAlgError, apply_auxiva.py:51); `status` then
+    holds the SETK_NUM_* value of every utterance of the last run()."""
+
+    def __init__(self, num_epochs=20, frame_len=512, frame_hop=256, center=True,
+                 round_power_of_two=True, window="hann", device=None, pcm16=False):
+        # no GPU / no library: setk_create fails here, loudly
+        self.ctx = _ffi.default_context(device)
+        self._slabs = None
+        self.pcm16 = bool(pcm16)
+        self.num_epochs = int(num_epochs)
+        self.status = []
+        n_fft = nextpow2(frame_len) if round_power_of_two else frame_len
+        self.stft = dict(frame_len=frame_len, frame_hop=frame_hop, n_fft=n_fft, center=center,
+                         window=stft_window(window, frame_len))
+        self.num_bins = n_fft // 2 + 1
+
+    def close(self):
+        """Give the slabs of run() back."""
+        b, self._slabs = self._slabs, None
+        if b:
+            b.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def run(self, utts):
+        ctx = self.ctx
+        out = [None] * len(utts)
+        self.status = [_ffi.NUM_OK] * len(utts)
+        if not len(utts):
+            return out
+        s = self.stft
+        ctx.stft_plan(s["frame_len"], s["frame_hop"], s["n_fft"], s["center"], s["window"])
+        groups = {}
+        for i, u in enumerate(utts):
+            groups.setdefault(_channels_and_size(u)[0], []).append(i)
+        if max(groups) > 8:
+            raise _ffi.SetkUnsupported(
+                f"AuxIVA on the device needs 1 <= channels <= 8 (got {max(groups)} channels)")
+        for C, idx in groups.items():
+            if s["n_fft"] == 512:
+                self._run_native(utts, C, idx, out)
+            else:
+                self._run_operators(utts, C, idx, out)
+        return out
+
+    def _run_native(self, utts, C, idx, out):
+        ctx = self.ctx
+        if self._slabs is None:
+            self._slabs = _Slabs(ctx)
+        b = self._slabs
+        esz = 2 if self.pcm16 else 4
+        aptr, ns, off_out, n_out = b.stage_audio(
+            [utts[i] for i in idx], C, lambda N: esz * C * ctx.istft_num_samples(ctx.num_frames(N)))
+        lens = [ctx.istft_num_samples(ctx.num_frames(N)) for N in ns]
+        status = np.zeros(len(idx), dtype=np.int32)
+        ctx.auxiva_batch(C, aptr, ns, self.num_epochs, [b.d_out + o for o in off_out], status=status,
+                         flags=_ffi.FLAG_OUT_PCM16 if self.pcm16 else 0, stream=b.stream)
+        host = b.fetch(n_out)
+        dt = np.int16 if self.pcm16 else np.float32
+        for k, i in enumerate(idx):
+            self.status[i] = int(status[k])
+            if status[k] == _ffi.NUM_OK:
+                L = lens[k]
+                out[i] = np.frombuffer(host[off_out[k]:off_out[k] + esz * C * L],
+                                       dtype=dt).reshape(C, L).copy()
+
+    def _run_operators(self, utts, C, idx, out):
+        """Transform sizes the batched call is not built for: the stand-alone operators
+        (setk_stft -> setk_auxiva -> setk_istft), one utterance at a time."""
+        ctx, F = self.ctx, self.num_bins
+        for i in idx:
+            samps = utts[i].to_float() if isinstance(utts[i], Pcm16Frames) else utts[i]
+            samps = np.ascontiguousarray(samps, dtype=np.float32).reshape(C, -1)
+            T = ctx.num_frames(samps.shape[1])
+            spec = np.empty((C, T, F), dtype=np.complex64)
+            ctx.stft(samps, spec)
+            sep = np.empty_like(spec)
+            status = np.zeros(F, dtype=np.int32)
+            ctx.auxiva(spec, C, T, F, self.num_epochs, sep, status=status)
+            self.status[i] = int(status.max())
+            if self.status[i] != _ffi.NUM_OK:
+                continue
+            wav = np.empty((C, ctx.istft_num_samples(T)), dtype=np.float32)
+            norm = np.full(C, np.max(np.abs(samps)), dtype=np.float32)
+            ctx.istft(sep, C, T, None, norm, wav)
+            out[i] = wavio_float_to_pcm16(wav) if self.pcm16 else wav
 
 
 class _Twin(object):
