@@ -12,8 +12,11 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libsetk_hip.so")
-SOURCES = ["pass1.hip", "pass1_mc.hip", "pass2.hip", "pass2_mc.hip", "solve.hip", "modular.hip", "cgmm.hip", "cgmm_bin.hip", "cgmm_k.hip", "wpe.hip", "auxiva.hip", "comm.hip", "hostio.hip", "capi.hip"]
-HEADERS = ["common.h", "fft512.h", "dpp.h", "covar_fold.h", "mcdft.h", "mcdft_tables.h", os.path.join("..", "..", "include", "setk_hip.h")]
+# The one list of translation units (`python setk_amd/build.py --units` prints it for the shell
+# recipes under tools/): the kernel units, then the C ABI front end by feature (capi.h).
+SOURCES = ["pass1.hip", "pass1_mc.hip", "pass2.hip", "pass2_mc.hip", "solve.hip", "modular.hip", "cgmm.hip", "cgmm_bin.hip", "cgmm_k.hip", "wpe.hip", "auxiva.hip", "comm.hip", "hostio.hip",
+           "capi_support.hip", "capi_handle.hip", "capi_stft.hip", "capi_modular.hip", "capi_fused.hip", "capi_cgmm.hip", "capi_wpe.hip", "capi_auxiva.hip"]
+HEADERS = ["common.h", "fft512.h", "dpp.h", "covar_fold.h", "mcdft.h", "mcdft_tables.h", "capi.h", os.path.join("..", "..", "include", "setk_hip.h")]
 ARCH = "gfx950"
 
 
@@ -68,8 +71,7 @@ def _build_locked(force, verbose):
              "cgmm_k.hip": [],
              "wpe.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"],
              "auxiva.hip": [],
-             "comm.hip": [],
-             "capi.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]}
+             "comm.hip": []}   # (the capi_*.hip units hold no kernel)
     # solve.hip and modular.hip hold a kernel each that must round like numpy operation by operation
     # (lu_refusal_kernel's LAPACK-order elimination; the Kaldi compressed-matrix decode) behind
     # `#pragma clang fp contract(off)`.  Plain `fast` lets the BACKEND fuse across the pragma (round 5's
@@ -106,4 +108,7 @@ def _build_locked(force, verbose):
 
 
 if __name__ == "__main__":
+    if "--units" in sys.argv:
+        print(" ".join(s[:-len(".hip")] for s in SOURCES))
+        sys.exit(0)
     print(build_library(force="--force" in sys.argv, verbose=True))

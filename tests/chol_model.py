@@ -1,6 +1,6 @@
 """
 numpy model of chol_lds (setk_amd/csrc/solve.hip) together with the embedding run_weights
-(capi.hip) and pack_covar_kernel use for 9..15 channels: the pivot floor at eps_f32 * max diag,
+(capi_modular.hip) and pack_covar_kernel use for 9..15 channels: the pivot floor at eps_f32 * max diag,
 the second attempt with 8 * floor added to the diagonal, the status, and blkdiag(M, pad * I) with
 pad = max_i Re M[i][i] of the bin.  The kernel's arithmetic is float64 and so is the model's.
 tests/test_solve_cases.py states the property the embedding has to give (no GPU needed); the GPU

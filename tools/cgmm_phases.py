@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Summarise a SETK_CGMM_TIMING dump (csrc/capi.hip): mean shader cycles per pass and bin of
+"""Summarise a SETK_CGMM_TIMING dump (csrc/capi_cgmm.hip): mean shader cycles per pass and bin of
 wave 0, per phase.  python tools/cgmm_phases.py <dump> [<dump of the product build>]"""
 import sys
 

@@ -17,8 +17,10 @@ else
 fi
 mkdir -p "$OUT"
 CLANG=/opt/rocm/lib/llvm/bin/clang++
-pids=""
-for u in pass1 pass1_mc pass2 pass2_mc solve modular cgmm cgmm_bin cgmm_k wpe auxiva comm hostio capi; do
+UNITS=$(python3 "$ROOT/setk_amd/build.py" --units)   # the one list of translation units
+pids=""; OBJS=""
+for u in $UNITS; do
+  OBJS="$OBJS $OUT/$u.o"
   src="$ROOT/setk_amd/csrc/$u.hip"
   if [ ! -f "$OUT/$u.o" ] || [ "$src" -nt "$OUT/$u.o" ] || [ -n "$(find "$ROOT/setk_amd/csrc" "$ROOT/include" -name '*.h' -newer "$OUT/$u.o")" ]; then
     /opt/rocm/bin/hipcc --cuda-host-only --offload-arch=gfx950 -O1 -std=c++17 -fPIC -Wno-unused-result $SAN \
@@ -31,7 +33,7 @@ $CLANG -x c++ -std=c++17 -O1 -fPIC -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include $S
   -c "$ROOT/tools/hoststub/hip_stub.cpp" -o "$OUT/hip_stub.o"
 # a host-only object still names its (absent) device image: give each name a dummy
 rm -f "$OUT/fatbin_dummies.o"
-nm --undefined-only "$OUT"/*.o | awk '/__hip_fatbin_/ {print "char " $2 "[16];"}' | sort -u > "$OUT/fatbin_dummies.c"
+nm --undefined-only $OBJS | awk '/__hip_fatbin_/ {print "char " $2 "[16];"}' | sort -u > "$OUT/fatbin_dummies.c"
 /opt/rocm/lib/llvm/bin/clang -fPIC -c "$OUT/fatbin_dummies.c" -o "$OUT/fatbin_dummies.o"
-$CLANG -shared -fPIC $SAN -o "$LIBOUT" "$OUT"/*.o
+$CLANG -shared -fPIC $SAN -o "$LIBOUT" $OBJS "$OUT/hip_stub.o" "$OUT/fatbin_dummies.o"
 echo "$LIBOUT"
