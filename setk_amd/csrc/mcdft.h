@@ -252,6 +252,88 @@ MC_DEV void forward_t(const float (&x)[8], const float (&w)[8], TileFn tile, con
         zi = mfma16(ai_h, bl, zi);
     }
 }
+// Two frames that share their window rows and operand tiles (the two frames of a hop-256
+// group of one channel): every tile is fetched ONCE and feeds the MFMA of frame 0, then the
+// one of frame 1, before it is dropped -- no tile outlives two MFMAs except the two hi tiles
+// of a stage, which wait for the lo halves as in forward_t.  Each frame's own chain into its
+// own accumulators is forward_t's (hi x T_h, hi x T_l, lo x T_h): bit-identical results; only
+// the interleaving of the two independent frames differs.  tile(i): as in forward_t;
+// twid(i): the rows TR, TI, TRI of the lane as f4.
+template <class TileFn, class TwidFn>
+MC_DEV void forward2_t(const float (&x0)[8], const float (&x1)[8], const float (&w)[8], TileFn tile, TwidFn twid,
+                       f4& zr0, f4& zi0, f4& a16_0, f4& zr1, f4& zi1, f4& a16_1) {
+    h8 xh0, xh1, xl0, xl1;
+    split8_mul_hi(x0, w, xh0);
+    split8_mul_hi(x1, w, xh1);
+    f4 dc0 = {0.f, 0.f, 0.f, 0.f}, ds0 = {0.f, 0.f, 0.f, 0.f};
+    f4 dc1 = {0.f, 0.f, 0.f, 0.f}, ds1 = {0.f, 0.f, 0.f, 0.f};
+    {
+        const h8 mc_h = tile(0), ms_h = tile(2);
+        dc0 = mfma16(xh0, mc_h, dc0);
+        dc1 = mfma16(xh1, mc_h, dc1);
+        ds0 = mfma16(xh0, ms_h, ds0);
+        ds1 = mfma16(xh1, ms_h, ds1);
+        {
+            const h8 mc_l = tile(1);
+            dc0 = mfma16(xh0, mc_l, dc0);
+            dc1 = mfma16(xh1, mc_l, dc1);
+        }
+        {
+            const h8 ms_l = tile(3);
+            ds0 = mfma16(xh0, ms_l, ds0);
+            ds1 = mfma16(xh1, ms_l, ds1);
+        }
+        split8_mul_lo(x0, w, xh0, xl0);
+        split8_mul_lo(x1, w, xh1, xl1);
+        dc0 = mfma16(xl0, mc_h, dc0);
+        dc1 = mfma16(xl1, mc_h, dc1);
+        ds0 = mfma16(xl0, ms_h, ds0);
+        ds1 = mfma16(xl1, ms_h, ds1);
+    }
+    a16_0 = ds0;
+    a16_1 = ds1;
+    // the twiddle rows arrive here, not before stage 1 (twelve registers the first stage needs)
+    __builtin_amdgcn_sched_barrier(0);
+    const f4 tr = twid(0), ti = twid(1), tri = twid(2);
+    float b0[8], b1[8];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        b0[r] = fmaf(dc0[r], tr[r], -ds0[r] * ti[r]);
+        b0[4 + r] = fmaf(dc0[r], ti[r], ds0[r] * tri[r]);
+        b1[r] = fmaf(dc1[r], tr[r], -ds1[r] * ti[r]);
+        b1[4 + r] = fmaf(dc1[r], ti[r], ds1[r] * tri[r]);
+    }
+    h8 bh0, bh1, bl0, bl1;
+    split8_hi(b0, bh0);
+    split8_hi(b1, bh1);
+    zr0 = (f4){0.f, 0.f, 0.f, 0.f};
+    zi0 = (f4){0.f, 0.f, 0.f, 0.f};
+    zr1 = (f4){0.f, 0.f, 0.f, 0.f};
+    zi1 = (f4){0.f, 0.f, 0.f, 0.f};
+    {
+        const h8 ar_h = tile(4), ai_h = tile(6);
+        zr0 = mfma16(ar_h, bh0, zr0);
+        zr1 = mfma16(ar_h, bh1, zr1);
+        zi0 = mfma16(ai_h, bh0, zi0);
+        zi1 = mfma16(ai_h, bh1, zi1);
+        {
+            const h8 ar_l = tile(5);
+            zr0 = mfma16(ar_l, bh0, zr0);
+            zr1 = mfma16(ar_l, bh1, zr1);
+        }
+        {
+            const h8 ai_l = tile(7);
+            zi0 = mfma16(ai_l, bh0, zi0);
+            zi1 = mfma16(ai_l, bh1, zi1);
+        }
+        split8_lo(b0, bh0, bl0);
+        split8_lo(b1, bh1, bl1);
+        zr0 = mfma16(ar_h, bl0, zr0);
+        zr1 = mfma16(ar_h, bl1, zr1);
+        zi0 = mfma16(ai_h, bl0, zi0);
+        zi1 = mfma16(ai_h, bl1, zi1);
+    }
+}
 MC_DEV void forward(const float (&x)[8], const float (&w)[8], const Fwd& K, f4& zr, f4& zi, f4& a16) {
     forward_t(x, w, [&](int i) -> h8 {
         switch (i) {
@@ -297,9 +379,9 @@ constexpr int kOddPitch = 20;  // floats per scratch row: 16-byte aligned, confl
 MC_DEV void store_a16(float* a16s, int j, int lane, f4 a16) {
     if ((lane & 15) == 0) *reinterpret_cast<f4*>(a16s + j * kOddPitch + (lane >> 4) * 4) = a16;
 }
-MC_DEV f4 odd_tile(const float* a16s, h8 ot_h, h8 ot_l, int lane, int nrows = 16) {
+// (odd_tile_row: column l % 16 takes scratch row j -- the caller's own mapping of columns to rows)
+MC_DEV f4 odd_tile_row(const float* a16s, h8 ot_h, h8 ot_l, int lane, int j) {
     const int g = lane >> 4;
-    const int j = (lane & 15) < nrows ? (lane & 15) : nrows - 1;  // unused columns repeat a valid row
     float v[8];
     const f4 v0 = *reinterpret_cast<const f4*>(a16s + j * kOddPitch + 8 * (g & 1));
     const f4 v1 = *reinterpret_cast<const f4*>(a16s + j * kOddPitch + 8 * (g & 1) + 4);
@@ -315,6 +397,10 @@ MC_DEV f4 odd_tile(const float* a16s, h8 ot_h, h8 ot_l, int lane, int nrows = 16
     d = mfma16(ot_h, bop, d);
     d = mfma16(ot_l, bop, d);  // T_lo x hi only (its K >= 16 half is zero)
     return d;
+}
+MC_DEV f4 odd_tile(const float* a16s, h8 ot_h, h8 ot_l, int lane, int nrows = 16) {
+    const int j = (lane & 15) < nrows ? (lane & 15) : nrows - 1;  // unused columns repeat a valid row
+    return odd_tile_row(a16s, ot_h, ot_l, lane, j);
 }
 
 // ---- per-lane tiles staged in LDS ([tile][lane] of 16 bytes: one conflict-free ds_read_b128) ----
@@ -388,6 +474,97 @@ MC_DEV void inverse(f4 yr, f4 yi, float e16, const Inv& K, f4& y0, f4& y1, int l
     float b[8];
     inverse_a(yr, yi, e16, K.br_h, K.br_l, K.bi_h, K.bi_l, K.tr, K.ti, b, lane);
     inverse_b(b, K.g0_h, K.g0_l, K.g1_h, K.g1_l, y0, y1);
+}
+
+// Two frames that share the inverse's tiles and twiddle rows: tile(i), i = 0..7: br_h br_l bi_h
+// bi_l g0_h g0_l g1_h g1_l, each fetched once and used for frame 0, then frame 1.  Each frame's
+// own chains are inverse_a's / inverse_b's (mm3_data_a, mm3_data_b): bit-identical results.
+template <class TileFn>
+MC_DEV void inverse2_a(f4 yr0, f4 yi0, float e16_0, f4 yr1, f4 yi1, float e16_1, TileFn tile, const float (&tr)[4],
+                       const float (&ti)[4], float (&b0)[8], float (&b1)[8], int lane) {
+    float a0[8], a1[8];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        a0[r] = yr0[r];
+        a0[4 + r] = yi0[r];
+        a1[r] = yr1[r];
+        a1[4 + r] = yi1[r];
+    }
+    h8 ah0, al0, ah1, al1;
+    split8(a0, ah0, al0);
+    split8(a1, ah1, al1);
+    f4 cr0 = {0.f, 0.f, 0.f, 0.f}, ci0 = {0.f, 0.f, 0.f, 0.f};
+    f4 cr1 = {0.f, 0.f, 0.f, 0.f}, ci1 = {0.f, 0.f, 0.f, 0.f};
+    {
+        const h8 br_h = tile(0);
+        cr0 = mfma16(ah0, br_h, cr0);
+        cr1 = mfma16(ah1, br_h, cr1);
+        cr0 = mfma16(al0, br_h, cr0);
+        cr1 = mfma16(al1, br_h, cr1);
+    }
+    {
+        const h8 br_l = tile(1);
+        cr0 = mfma16(ah0, br_l, cr0);
+        cr1 = mfma16(ah1, br_l, cr1);
+    }
+    {
+        const h8 bi_h = tile(2);
+        ci0 = mfma16(ah0, bi_h, ci0);
+        ci1 = mfma16(ah1, bi_h, ci1);
+        ci0 = mfma16(al0, bi_h, ci0);
+        ci1 = mfma16(al1, bi_h, ci1);
+    }
+    {
+        const h8 bi_l = tile(3);
+        ci0 = mfma16(ah0, bi_l, ci0);
+        ci1 = mfma16(ah1, bi_l, ci1);
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        // conj twiddle: (cr + i ci)(tr - i ti)
+        b0[r] = fmaf(cr0[r], tr[r], ci0[r] * ti[r]);
+        b0[4 + r] = fmaf(ci0[r], tr[r], -cr0[r] * ti[r]);
+        b1[r] = fmaf(cr1[r], tr[r], ci1[r] * ti[r]);
+        b1[4 + r] = fmaf(ci1[r], tr[r], -cr1[r] * ti[r]);
+    }
+    if (lane < 16) {  // the (im, k1 = 0) slot carries E16
+        b0[4] = e16_0;
+        b1[4] = e16_1;
+    }
+}
+template <class TileFn>
+MC_DEV void inverse2_b(const float (&b0)[8], const float (&b1)[8], TileFn tile, f4& y0_0, f4& y1_0, f4& y0_1, f4& y1_1) {
+    h8 bh0, bl0, bh1, bl1;
+    split8(b0, bh0, bl0);
+    split8(b1, bh1, bl1);
+    y0_0 = (f4){0.f, 0.f, 0.f, 0.f};
+    y1_0 = (f4){0.f, 0.f, 0.f, 0.f};
+    y0_1 = (f4){0.f, 0.f, 0.f, 0.f};
+    y1_1 = (f4){0.f, 0.f, 0.f, 0.f};
+    {
+        const h8 g0_h = tile(4);
+        y0_0 = mfma16(g0_h, bh0, y0_0);
+        y0_1 = mfma16(g0_h, bh1, y0_1);
+        y0_0 = mfma16(g0_h, bl0, y0_0);
+        y0_1 = mfma16(g0_h, bl1, y0_1);
+    }
+    {
+        const h8 g0_l = tile(5);
+        y0_0 = mfma16(g0_l, bh0, y0_0);
+        y0_1 = mfma16(g0_l, bh1, y0_1);
+    }
+    {
+        const h8 g1_h = tile(6);
+        y1_0 = mfma16(g1_h, bh0, y1_0);
+        y1_1 = mfma16(g1_h, bh1, y1_1);
+        y1_0 = mfma16(g1_h, bl0, y1_0);
+        y1_1 = mfma16(g1_h, bl1, y1_1);
+    }
+    {
+        const h8 g1_l = tile(7);
+        y1_0 = mfma16(g1_l, bh0, y1_0);
+        y1_1 = mfma16(g1_l, bh1, y1_1);
+    }
 }
 
 // E16[n2] of SIXTEEN frames: in lane (j = l % 16, g) v[e] = hi/lo source: the 8 odd-family

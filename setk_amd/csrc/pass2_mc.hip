@@ -6,14 +6,16 @@
 // (libs/utils.py:142-173 -> librosa.istft 0.8.1: irfft, * window, overlap-add,
 // / sum(window^2) where > tiny, trim n_fft/2; the inf-norm rescale is scale_kernel).
 //
-// One wavefront owns a run of consecutive frames, one frame at a time: it transforms the C
-// channels one after the other (12 MFMA + ~90 VALU wave-instructions each; the samples two
-// transforms ahead in flight), folds conj(w_c) X_c into four complex accumulators per lane (the
-// lane's bins are fixed, its weights come from an LDS table as one base address +
-// immediates), adds the odd family X[16 + 32 q] of all channels from ONE extra tile per frame,
-// scales the frame's spectrum by a power of two into the fp16 operand range,
-// inverse-transforms (12 MFMA), windows, and completes one block of hop output samples per
-// frame from its own registers (hop = n_fft / 2: see the kernel).  No frame slots, no
+// One wavefront owns a run of consecutive frames, two frames (a group) at a time: it transforms
+// the C channels one after the other, both frames of a channel as a pair (24 MFMA; every operand
+// tile, window row and twiddle row read from LDS once for the two; the next channel's twelve
+// samples per lane in flight), folds conj(w_c) X_c into four complex accumulators per lane and
+// frame (the lane's bins are fixed, its weights come from an LDS table as one base address +
+// immediates), adds the odd family X[16 + 32 q] of all channels of both frames from ONE extra
+// tile per group, scales each frame's spectrum by a power of two into the fp16 operand range,
+// inverse-transforms the pair (24 MFMA over one read of the inverse's tiles), windows, and
+// completes one block of hop output samples per frame from its own registers (hop = n_fft / 2:
+// see the kernel).  No frame slots, no
 // workgroup barrier, no overlap-add loop; ~128 VGPRs: four waves per SIMD where the butterfly
 // kernel ran two.  Other hops keep pass2.hip.
 #include "common.h"
@@ -40,16 +42,17 @@ constexpr int p2mc_threads(bool pcm) { return pcm ? 1024 : 512; }
 // words) + OT_H, OT_L + the forward's 8 + window 2 + twiddles 3
 constexpr int kP2McTiles = 25;
 // LDS plan (bytes): wtab C * 257 * 8 | operand tiles 25 * 1024 | synthesis rows
-// 2048 | a16 scratch NW * 8 * kOddPitch * 4 | yodd NW * 16 * 4 | red 64
+// 2048 | a16 scratch NW * R * 8 * kOddPitch * 4 | yodd NW * R * 16 * 4 | red 64
 // | PCM carry NW * C * 64 * 8
 size_t pass2_mc_lds_bytes(int C, bool pcm) {
     const size_t nw = p2mc_threads(pcm) / 64;
     const size_t wt = ((size_t)C * kBins * sizeof(cf) + 15) & ~(size_t)15;
     return wt + kP2McTiles * 1024 + 2048 + nw * kP2McGroup * 8 * mc::kOddPitch * sizeof(float) +
-           nw * 16 * sizeof(float) + 64 + (pcm ? nw * C * 64 * sizeof(uint2) : 0);
+           nw * kP2McGroup * 16 * sizeof(float) + 64 + (pcm ? nw * C * 64 * sizeof(uint2) : 0);
 }
 
-// sum over the first 8 lanes of every 16-lane row, result in lanes 0..7 of the row
+// sum over each 8-lane half of every 16-lane row on its own (the three steps stay inside a half),
+// result in all lanes of the half: lanes 0..7 = frame 0 of a group, 8..15 = frame 1
 SETK_DEV float row8_sum(float x) {
     int v = __builtin_bit_cast(int, x);
     x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xf, 0xf, true));   // j ^ 1
@@ -107,8 +110,8 @@ __global__ __launch_bounds__(p2mc_threads(PCM), kP2McWavesPerSimd) void beamform
     p += 2048;
     float* a16s = reinterpret_cast<float*>(p);  // [NW][R][8][kOddPitch]
     p += (size_t)NW * kP2McGroup * 8 * mc::kOddPitch * sizeof(float);
-    float* yodd_s = reinterpret_cast<float*>(p);  // [NW][16]
-    p += NW * 16 * sizeof(float);
+    float* yodd_s = reinterpret_cast<float*>(p);  // [NW][R][16]
+    p += NW * kP2McGroup * 16 * sizeof(float);
     float* red = reinterpret_cast<float*>(p);
     p += 64;
     uint2* carry_s = reinterpret_cast<uint2*>(p);  // PCM: [NW][C][64] packed int16 x 4
@@ -165,12 +168,9 @@ __global__ __launch_bounds__(p2mc_threads(PCM), kP2McWavesPerSimd) void beamform
                            a.mc_syn[(4 * hf + 2) * 64 + l] * out_sc, a.mc_syn[(4 * hf + 3) * 64 + l] * out_sc};
     }
     struct { float tr[4], ti[4]; } K;  // (the inverse's conjugate twiddles: re-read there)
-    float* yoddw = yodd_s + wave * 16;
+    float* yoddw = yodd_s + wave * kP2McGroup * 16;  // [R][16]
     const int lane_bin = mc::bin_of(c16, g, 0);
     const cf* wl = wtab + lane_bin;                       // + c * F + 32 r
-    const int jo = c16 < C ? c16 : 0;                     // odd-family tile: column = channel
-    const cf* wo = wtab + jo * F + 16 + 64 * g;           // w_j[16 + 32 (2 g)], [+ 32] the next
-    const bool odd_on = c16 < C;
     const int lane_n = 64 * g + c16;                      // sample 16 (4 g + r) + n2 = lane_n + 16 r
     float omax = 0.f;
     __syncthreads();  // tables ready (the only workgroup barrier before the epilogue)
@@ -183,13 +183,13 @@ __global__ __launch_bounds__(p2mc_threads(PCM), kP2McWavesPerSimd) void beamform
 
     // Channel-major over groups of R consecutive frames: with hop = n_fft / 2 frame t + 1 shares
     // its first half with frame t -- the same lane's registers (mc::sample_of) -- so inside a
-    // group a transform loads four new samples per lane, not eight, and the weights of a channel
-    // are read once per group.  The R spectra of the group accumulate in registers.
+    // group's pair of transforms takes twelve samples per lane, not sixteen, and the weights, the
+    // operand tiles and the table rows of a channel are read once per group.  The R spectra of the
+    // group accumulate in registers.
     constexpr int R = kP2McGroup;
     float* a16g = a16s + wave * R * 8 * mc::kOddPitch;  // [R][8 channels][kOddPitch]
     float carry[4] = {0.f, 0.f, 0.f, 0.f};
-    // loaders: a whole frame (8 registers) / the second half of a frame (registers 4..7).
-    // EDGE: some sample of the group lies outside the signal (numpy "reflect" padding) -- the
+    // EDGE (load_pair): some sample of the group lies outside the signal (numpy "reflect" padding) -- the
     // first and the last group of an utterance; frames past the last one repeat it (computed
     // to keep the group uniform, never emitted).
     // channel c of the utterance: float32 [C][N] or int16 [C][ch_stride] (the conversion is the
@@ -201,74 +201,63 @@ __global__ __launch_bounds__(p2mc_threads(PCM), kP2McWavesPerSimd) void beamform
     // PCM carry: the lane's own four samples of the half frame a group ends with, per channel --
     // a thread reads back exactly what it wrote (program order suffices, no barrier)
     uint2* carry_l = carry_s + (size_t)wave * C * 64 + lane;  // + 64 c
-    auto load_full = [&](float (&v)[8], int t, int c, auto edge) __attribute__((always_inline)) {
+    // loader: the two frames of a group of channel c -- three half frames, 12 samples per lane
+    // (v[0..3], v[4..7]: frame t0; v[4..7], v[8..11]: frame t0 + 1).  PCM: the last half frame
+    // stays raw in nr (it is packed for the carry where it is consumed), v[8..11] are unused.
+    auto load_pair = [&](float (&v)[12], int (&nr)[4], int t0, int c, auto edge) __attribute__((always_inline)) {
+        const auto x = chan(c);
+        const int o = 64 * g + c16;
+        const int s0 = min(t0, T - 1) * hop - a.g.pad, s1 = min(t0 + 1, T - 1) * hop - a.g.pad + 256;
         if constexpr (PCM) {
             // first half: what this lane parked at the end of the previous group (or the prefill
-            // before the first); second half: the only samples of the frame not seen yet
+            // before the first); the other two: the only samples of the group not seen yet
             const uint2 pk = carry_l[64 * c];
             v[0] = (float)(short)(pk.x & 0xffff);
             v[1] = (float)((int)pk.x >> 16);
             v[2] = (float)(short)(pk.y & 0xffff);
             v[3] = (float)((int)pk.y >> 16);
-            const auto x = chan(c);
-            const int s0 = min(t, T - 1) * hop - a.g.pad + 256, o = 64 * g + c16;
             if (!decltype(edge)::value) {
 #pragma unroll
-                for (int e = 0; e < 4; ++e) v[4 + e] = x[s0 + o + 16 * e];
+                for (int e = 0; e < 4; ++e) {
+                    v[4 + e] = x[s0 + o + 256 + 16 * e];
+                    nr[e] = x[s1 + o + 16 * e];
+                }
             } else {
 #pragma unroll
-                for (int e = 0; e < 4; ++e) v[4 + e] = x[reflect_index(s0 + o + 16 * e, n_samp)];
+                for (int e = 0; e < 4; ++e) {
+                    v[4 + e] = x[reflect_index(s0 + o + 256 + 16 * e, n_samp)];
+                    nr[e] = x[reflect_index(s1 + o + 16 * e, n_samp)];
+                }
             }
         } else {
-            const auto x = chan(c);
-            const int s0 = min(t, T - 1) * hop - a.g.pad, o = 64 * g + c16;
             if (!decltype(edge)::value) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     // both halves of a group's first frame are read for the last time here (the
                     // first one is the re-read of what the previous group fetched as ITS last
                     // half): a streaming hint keeps them from pushing the halves that WILL be read
-                    // again -- load_half's -- out of the XCD's L2
+                    // again -- the group's last -- out of the XCD's L2
                     v[e] = __builtin_nontemporal_load(&x[s0 + o + 16 * e]);
                     v[4 + e] = __builtin_nontemporal_load(&x[s0 + o + 256 + 16 * e]);
                 }
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[8 + e] = x[s1 + o + 16 * e];
             } else {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     v[e] = x[reflect_index(s0 + o + 16 * e, n_samp)];
                     v[4 + e] = x[reflect_index(s0 + o + 256 + 16 * e, n_samp)];
+                    v[8 + e] = x[reflect_index(s1 + o + 16 * e, n_samp)];
                 }
             }
         }
     };
-    // PCM: the second half as raw 16-bit samples, converted and packed for the carry where consumed
-    auto load_half_raw = [&](int (&r)[4], int t, int c, auto edge) __attribute__((always_inline)) {
-        const auto x = chan(c);
-        const int s0 = min(t, T - 1) * hop - a.g.pad + 256, o = 64 * g + c16;
-        if (!decltype(edge)::value) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) r[e] = x[s0 + o + 16 * e];
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) r[e] = x[reflect_index(s0 + o + 16 * e, n_samp)];
-        }
-    };
-    auto load_half = [&](float (&v)[8], int t, int c, auto edge) __attribute__((always_inline)) {
-        const auto x = chan(c);
-        const int s0 = min(t, T - 1) * hop - a.g.pad + 256, o = 64 * g + c16;
-        if (!decltype(edge)::value) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[4 + e] = x[s0 + o + 16 * e];
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[4 + e] = x[reflect_index(s0 + o + 16 * e, n_samp)];
-        }
-    };
     mc::f4 yr[R], yi[R];
-    // the R transforms of every channel of one group; `nxt` arrives holding frame (t0, channel 0)
-    // and leaves holding frame (t0 + R, channel 0)
-    float nxt[8];
-    int nraw[4];  // PCM: the half frame in flight, as loaded
+    // the pair of transforms of every channel of one group; `nxt` / `nraw` arrive holding the
+    // group (t0, channel 0) and leave holding (t0 + R, channel 0) once request_group has run
+    static_assert(R == 2, "the paired transform and the LDS carry are written for groups of two frames");
+    float nxt[12];
+    int nraw[4];  // PCM: the group's last half frame, as loaded
     auto group = [&](int t0, auto edge) __attribute__((always_inline)) {
 #pragma unroll
         for (int k = 0; k < R; ++k) {
@@ -277,61 +266,50 @@ __global__ __launch_bounds__(p2mc_threads(PCM), kP2McWavesPerSimd) void beamform
         }
 #pragma unroll 1
         for (int c = 0; c < C; ++c) {
+            float x0[8], x1[8];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                x0[e] = nxt[e];
+                x0[4 + e] = nxt[4 + e];
+                x1[e] = nxt[4 + e];
+                if constexpr (PCM) x1[4 + e] = (float)nraw[e];
+                else x1[4 + e] = nxt[8 + e];
+            }
+            if constexpr (PCM) {
+                // the group's last half frame is the next group's first
+                carry_l[64 * c] = make_uint2(__builtin_amdgcn_perm((unsigned)nraw[1], (unsigned)nraw[0], 0x05040100u),
+                                             __builtin_amdgcn_perm((unsigned)nraw[3], (unsigned)nraw[2], 0x05040100u));
+            }
+            // the next channel's twelve samples travel while this pair runs (the next group's
+            // channel 0 is requested after the group: its span decides the path)
+            if (c + 1 < C) load_pair(nxt, nraw, t0, c + 1, edge);
+            mc::f4 zr0, zi0, a16_0, zr1, zi1, a16_1;
+            {
+                asm volatile("" ::: "memory");  // tiles and tables: once per channel and group, not kept
+                const mc::f4 w0 = __builtin_bit_cast(mc::f4, tiles[20 * 64 + lane]);
+                const mc::f4 w1 = __builtin_bit_cast(mc::f4, tiles[21 * 64 + lane]);
+                const float win[8] = {w0[0], w0[1], w0[2], w0[3], w1[0], w1[1], w1[2], w1[3]};
+                mc::forward2_t(x0, x1, win, [&](int i) { return mc::lds_h8(tiles, 12 + i, lane); },
+                               [&](int i) { return __builtin_bit_cast(mc::f4, tiles[(22 + i) * 64 + lane]); },
+                               zr0, zi0, a16_0, zr1, zi1, a16_1);
+            }
+            __builtin_amdgcn_sched_barrier(0);
             asm volatile("" ::: "memory");  // the weights are re-read per group, not kept (64 registers)
             const cf* wc = wl + c * F;
             cf w[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) w[r] = wc[32 * r];
-            float x[8];
+            mc::store_a16(a16g, c, lane, a16_0);
+            mc::store_a16(a16g + 8 * mc::kOddPitch, c, lane, a16_1);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) x[e] = nxt[e];
-#pragma unroll
-            for (int k = 0; k < R; ++k) {
-                // what comes next travels while this transform runs: the second half of the
-                // next frame of the group, or the first frame of the next channel / group
-                if (k + 1 < R) {
-                    if constexpr (PCM) load_half_raw(nraw, t0 + k + 1, c, edge);
-                    else load_half(nxt, t0 + k + 1, c, edge);
-                } else if (c + 1 < C) {
-                    load_full(nxt, t0, c + 1, edge);
-                }
-                mc::f4 zr, zi, a16;
-                {
-                    asm volatile("" ::: "memory");
-                    const mc::f4 w0 = __builtin_bit_cast(mc::f4, tiles[20 * 64 + lane]);
-                    const mc::f4 w1 = __builtin_bit_cast(mc::f4, tiles[21 * 64 + lane]);
-                    const mc::f4 q0 = __builtin_bit_cast(mc::f4, tiles[22 * 64 + lane]);
-                    const mc::f4 q1 = __builtin_bit_cast(mc::f4, tiles[23 * 64 + lane]);
-                    const mc::f4 q2 = __builtin_bit_cast(mc::f4, tiles[24 * 64 + lane]);
-                    const float win[8] = {w0[0], w0[1], w0[2], w0[3], w1[0], w1[1], w1[2], w1[3]};
-                    const float tr[4] = {q0[0], q0[1], q0[2], q0[3]}, ti[4] = {q1[0], q1[1], q1[2], q1[3]},
-                                tri[4] = {q2[0], q2[1], q2[2], q2[3]};
-                    mc::forward_t(x, win, [&](int i) { return mc::lds_h8(tiles, 12 + i, lane); }, tr, ti, tri, zr, zi, a16);
-                }
-                mc::store_a16(a16g + k * 8 * mc::kOddPitch, c, lane, a16);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    yr[k][r] = fmaf(zr[r], w[r].x, fmaf(zi[r], w[r].y, yr[k][r]));
-                    yi[k][r] = fmaf(zi[r], w[r].x, fmaf(-zr[r], w[r].y, yi[k][r]));
-                }
-                if (k + 1 < R) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        x[e] = x[4 + e];
-                        if constexpr (PCM) x[4 + e] = (float)nraw[e];
-                        else x[4 + e] = nxt[4 + e];
-                    }
-                    if constexpr (PCM) {
-                        // the group's last half frame is the next group's first: R == 2, k == 0
-                        static_assert(R == 2, "the LDS carry is written for groups of two frames");
-                        carry_l[64 * c] = make_uint2(__builtin_amdgcn_perm((unsigned)nraw[1], (unsigned)nraw[0], 0x05040100u),
-                                                     __builtin_amdgcn_perm((unsigned)nraw[3], (unsigned)nraw[2], 0x05040100u));
-                    }
-                }
-                // one transform at a time: interleaved by the scheduler, the R unrolled
-                // transforms keep R working sets alive and spill 150 registers
-                __builtin_amdgcn_sched_barrier(0);
+            for (int r = 0; r < 4; ++r) {
+                yr[0][r] = fmaf(zr0[r], w[r].x, fmaf(zi0[r], w[r].y, yr[0][r]));
+                yi[0][r] = fmaf(zi0[r], w[r].x, fmaf(-zr0[r], w[r].y, yi[0][r]));
+                yr[1][r] = fmaf(zr1[r], w[r].x, fmaf(zi1[r], w[r].y, yr[1][r]));
+                yi[1][r] = fmaf(zi1[r], w[r].x, fmaf(-zr1[r], w[r].y, yi[1][r]));
             }
+            // one pair at a time: the scheduler must not pull the next channel's pair in
+            __builtin_amdgcn_sched_barrier(0);
         }
     };
     auto span_is_edge = [&](int t0) {
@@ -339,8 +317,8 @@ __global__ __launch_bounds__(p2mc_threads(PCM), kP2McWavesPerSimd) void beamform
         return lo < 0 || hi > n_samp || t0 + R > T;
     };
     auto request_group = [&](int t0) __attribute__((always_inline)) {
-        if (span_is_edge(t0)) load_full(nxt, t0, 0, std::true_type());
-        else load_full(nxt, t0, 0, std::false_type());
+        if (span_is_edge(t0)) load_pair(nxt, nraw, t0, 0, std::true_type());
+        else load_pair(nxt, nraw, t0, 0, std::false_type());
     };
     if constexpr (PCM) {
         // the first half of the wave's first frame, every channel: from here on a group reads two
@@ -367,97 +345,133 @@ __global__ __launch_bounds__(p2mc_threads(PCM), kP2McWavesPerSimd) void beamform
         if (span_is_edge(t0)) group(t0, std::true_type());
         else group(t0, std::false_type());
         if (t0 + R < tb) request_group(t0 + R);  // (issued here: its span decides the path)
+        // ---- the tail of both frames at once: every once-per-frame tile is read once per group.
+        //      Frame 1 of a short group (nf < R) is computed and dropped. ----
+        const int t1 = min(t0 + 1, T - 1);  // (the mask row of a frame past the end: any valid one)
+        // the lane's once-per-group addresses are formed here from an opaque copy of the lane
+        // index (a dozen integer operations per group): as loop invariants they take registers
+        // the transforms need and end up in scratch
+        int lt = lane;
+        asm volatile("" : "+v"(lt));
+        const int kf = (lt >> 3) & 1, co = lt & 7, c16 = lt & 15, g = lt >> 4;  // odd-family tile: column = 8 x frame + channel
+        const bool odd_on = co < C;
+        const cf* wo = wtab + (odd_on ? co : 0) * F + 16 + 64 * g;  // w_j[16 + 32 (2 g)], [+ 32] the next
+        const int orow = 8 * kf + (odd_on ? co : C - 1);            // unused columns repeat a valid row
+        // ---- odd family of all channels of both frames: ONE tile, column 8 k + c = frame k,
+        //      channel c; then the sum over the channel lanes of each 8-lane half ----
+        float yo[4];
+        {
+            asm volatile("" ::: "memory");  // the once-per-group tiles are re-read, not kept
+            const mc::f4 d = mc::odd_tile_row(a16g, mc::lds_h8(tiles, 10, lane), mc::lds_h8(tiles, 11, lane), lane, orow);
+            const cf w0 = wo[0], w1 = wo[32];
+            yo[0] = odd_on ? fmaf(d[0], w0.x, d[1] * w0.y) : 0.f;
+            yo[1] = odd_on ? fmaf(d[1], w0.x, -d[0] * w0.y) : 0.f;
+            yo[2] = odd_on ? fmaf(d[2], w1.x, d[3] * w1.y) : 0.f;
+            yo[3] = odd_on ? fmaf(d[3], w1.x, -d[2] * w1.y) : 0.f;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) yo[i] = row8_sum(yo[i]);
+        }
+        mc::f4 fr[R], fi[R];
+#pragma unroll
+        for (int k = 0; k < R; ++k) {
+            fr[k] = yr[k];
+            fi[k] = yi[k];
+        }
+        // ---- optional post-mask ----
+        if (post_mask) {
+            const float* mrow = ud.mask_s + (size_t)t0 * F;
+            // the lane's offsets are formed here, against the row's scalar base: hoisted out of
+            // the group loop they are 64-bit addresses per lane that live in scratch
+            const unsigned dm = (unsigned)(t1 - t0) * F;  // frame 1's row
+            unsigned mo = (unsigned)lane_bin, mq = 16u + 64u * (unsigned)g + (kf ? dm : 0u);
+            asm volatile("" : "+v"(mo), "+v"(mq));
+#pragma unroll
+            for (int k = 0; k < R; ++k) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    float m = mrow[mo + (k ? dm : 0u) + 32 * r];
+                    if (clamp) m = fminf(m, 1.f);
+                    fr[k][r] *= m;
+                    fi[k][r] *= m;
+                }
+            }
+            float m0 = mrow[mq], m1 = mrow[mq + 32];
+            if (clamp) { m0 = fminf(m0, 1.f); m1 = fminf(m1, 1.f); }
+            yo[0] *= m0;
+            yo[1] *= m0;
+            yo[2] *= m1;
+            yo[3] *= m1;
+        }
+        // ---- power-of-two scale of each frame into the fp16 operand range: max < 2^11 ----
+        const float yom = fmaxf(fmaxf(fabsf(yo[0]), fabsf(yo[1])), fmaxf(fabsf(yo[2]), fabsf(yo[3])));
+        float sc[R], isc[R];
+#pragma unroll
+        for (int k = 0; k < R; ++k) {
+            // only Re Y[0], Re Y[256] reach the inverse (numpy irfft drops their imaginary parts)
+            fi[k][0] = (lane == 0) ? 0.f : fi[k][0];
+            fi[k][3] = (lane == 32) ? 0.f : fi[k][3];
+            float mxl = (kf == k) ? yom : 0.f;  // the odd family of frame k sits in its half of the rows
+#pragma unroll
+            for (int r = 0; r < 4; ++r) mxl = fmaxf(mxl, fmaxf(fabsf(fr[k][r]), fabsf(fi[k][r])));
+            const float mxw = wave_max_nonneg(mxl);
+            int ex = (int)((__builtin_bit_cast(unsigned, mxw) >> 23) & 0xff);  // mxw < 2^(ex - 126)
+            ex = ex < 16 ? 16 : (ex > 250 ? 250 : ex);                         // (zero / tiny / huge frames)
+            sc[k] = __builtin_bit_cast(float, (unsigned)(264 - ex) << 23);     // 2^(137 - ex)
+            isc[k] = __builtin_bit_cast(float, (unsigned)(ex - 10) << 23);
+        }
+        // ---- E16 of the odd family: its tile takes frames as rows; the group's are rows 0, 1 ----
+        {
+            const float scl = kf ? sc[1] : sc[0];
+            if ((c16 & 7) == 0) *reinterpret_cast<mc::f4*>(yoddw + 16 * kf + 4 * g) = (mc::f4){yo[0] * scl, yo[1] * scl, yo[2] * scl, yo[3] * scl};
+        }
+        float e16[R];
+        {
+            float v[8];
+            const mc::f4 v0 = *reinterpret_cast<const mc::f4*>(yoddw + 16 * (c16 & 1) + 8 * (g & 1));
+            const mc::f4 v1 = *reinterpret_cast<const mc::f4*>(yoddw + 16 * (c16 & 1) + 8 * (g & 1) + 4);
+            const float rowsel = c16 < R ? 1.f : 0.f;  // rows 2..15 of the tile are unused
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                v[e] = v0[e] * rowsel;
+                v[4 + e] = v1[e] * rowsel;
+            }
+            const mc::f4 d = mc::inv_odd_tile(v, mc::lds_h8(tiles, 8, lane), mc::lds_h8(tiles, 9, lane), lane);
+            e16[0] = d[0];  // lanes g == 0: E16[n2 = l % 16] of row 0, row 1
+            e16[1] = d[1];
+        }
+#pragma unroll
+        for (int k = 0; k < R; ++k) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                fr[k][r] *= sc[k];
+                fi[k][r] *= sc[k];
+            }
+        }
+        float bmid0[8], bmid1[8];
+        {
+            const mc::f4 tt0 = __builtin_bit_cast(mc::f4, tiles[22 * 64 + lane]);
+            const mc::f4 tt1 = __builtin_bit_cast(mc::f4, tiles[23 * 64 + lane]);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                K.tr[r] = tt0[r];
+                K.ti[r] = tt1[r];
+            }
+        }
+        auto inv_tile = [&](int i) { return mc::lds_h8(tiles, i, lane); };
+        mc::inverse2_a(fr[0], fi[0], e16[0], fr[1], fi[1], e16[1], inv_tile, K.tr, K.ti, bmid0, bmid1, lane);
+        asm volatile("" ::: "memory");
+        mc::f4 y0[R], y1[R];
+        mc::inverse2_b(bmid0, bmid1, inv_tile, y0[0], y1[0], y0[1], y1[1]);
+        // ---- block t = first half of frame t + second half of frame t - 1 (the carry); the
+        //      rows hold window / 512 / sum(window^2) x the back-scale of the spectra ----
+        const mc::f4 s0 = synr[lane], s1 = synr[64 + lane];
 #pragma unroll
         for (int k = 0; k < R; ++k) {
             if (k >= nf) break;
             const int t = t0 + k;
-            // ---- odd family of all channels: one tile, then the sum over the channel lanes ----
-            float yo[4];
-            {
-                asm volatile("" ::: "memory");  // the once-per-frame tiles are re-read, not kept
-                const mc::f4 d = mc::odd_tile(a16g + k * 8 * mc::kOddPitch, mc::lds_h8(tiles, 10, lane),
-                                              mc::lds_h8(tiles, 11, lane), lane, C);
-                const cf w0 = wo[0], w1 = wo[32];
-                yo[0] = odd_on ? fmaf(d[0], w0.x, d[1] * w0.y) : 0.f;
-                yo[1] = odd_on ? fmaf(d[1], w0.x, -d[0] * w0.y) : 0.f;
-                yo[2] = odd_on ? fmaf(d[2], w1.x, d[3] * w1.y) : 0.f;
-                yo[3] = odd_on ? fmaf(d[3], w1.x, -d[2] * w1.y) : 0.f;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) yo[i] = row8_sum(yo[i]);
-            }
-            mc::f4 fr = yr[k], fi = yi[k];
-            // ---- optional post-mask ----
-            if (post_mask) {
-                const float* mrow = ud.mask_s + (size_t)t * F;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    float m = mrow[lane_bin + 32 * r];
-                    if (clamp) m = fminf(m, 1.f);
-                    fr[r] *= m;
-                    fi[r] *= m;
-                }
-                float m0 = mrow[16 + 64 * g], m1 = mrow[48 + 64 * g];
-                if (clamp) { m0 = fminf(m0, 1.f); m1 = fminf(m1, 1.f); }
-                yo[0] *= m0;
-                yo[1] *= m0;
-                yo[2] *= m1;
-                yo[3] *= m1;
-            }
-            // only Re Y[0], Re Y[256] reach the inverse (numpy irfft drops their imaginary parts)
-            fi[0] = (lane == 0) ? 0.f : fi[0];
-            fi[3] = (lane == 32) ? 0.f : fi[3];
-            // ---- power-of-two scale of the frame into the fp16 operand range: max < 2^11 ----
-            float mxl = fmaxf(fmaxf(fabsf(yo[0]), fabsf(yo[1])), fmaxf(fabsf(yo[2]), fabsf(yo[3])));
-#pragma unroll
-            for (int r = 0; r < 4; ++r) mxl = fmaxf(mxl, fmaxf(fabsf(fr[r]), fabsf(fi[r])));
-            const float mxw = wave_max_nonneg(mxl);
-            int ex = (int)((__builtin_bit_cast(unsigned, mxw) >> 23) & 0xff);  // mxw < 2^(ex - 126)
-            ex = ex < 16 ? 16 : (ex > 250 ? 250 : ex);                         // (zero / tiny / huge frames)
-            const float sc = __builtin_bit_cast(float, (unsigned)(264 - ex) << 23);   // 2^(137 - ex)
-            const float isc = __builtin_bit_cast(float, (unsigned)(ex - 10) << 23);
-            // ---- E16 of the odd family: its tile takes frames as rows; this frame is row 0 ----
-            if (c16 == 0) *reinterpret_cast<mc::f4*>(yoddw + 4 * g) = (mc::f4){yo[0] * sc, yo[1] * sc, yo[2] * sc, yo[3] * sc};
-            float e16;
-            {
-                float v[8];
-                const mc::f4 v0 = *reinterpret_cast<const mc::f4*>(yoddw + 8 * (g & 1));
-                const mc::f4 v1 = *reinterpret_cast<const mc::f4*>(yoddw + 8 * (g & 1) + 4);
-                const float rowsel = c16 == 0 ? 1.f : 0.f;  // rows 1..15 of the tile are unused
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    v[e] = v0[e] * rowsel;
-                    v[4 + e] = v1[e] * rowsel;
-                }
-                const mc::f4 d = mc::inv_odd_tile(v, mc::lds_h8(tiles, 8, lane), mc::lds_h8(tiles, 9, lane), lane);
-                e16 = d[0];  // lanes g == 0: E16[n2 = l % 16] of row 0
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                fr[r] *= sc;
-                fi[r] *= sc;
-            }
-            float bmid[8];
-            {
-                const mc::f4 tt0 = __builtin_bit_cast(mc::f4, tiles[22 * 64 + lane]);
-                const mc::f4 tt1 = __builtin_bit_cast(mc::f4, tiles[23 * 64 + lane]);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    K.tr[r] = tt0[r];
-                    K.ti[r] = tt1[r];
-                }
-            }
-            mc::inverse_a(fr, fi, e16, mc::lds_h8(tiles, 0, lane), mc::lds_h8(tiles, 1, lane),
-                          mc::lds_h8(tiles, 2, lane), mc::lds_h8(tiles, 3, lane), K.tr, K.ti, bmid, lane);
-            asm volatile("" ::: "memory");
-            mc::f4 y0, y1;
-            mc::inverse_b(bmid, mc::lds_h8(tiles, 4, lane), mc::lds_h8(tiles, 5, lane),
-                          mc::lds_h8(tiles, 6, lane), mc::lds_h8(tiles, 7, lane), y0, y1);
-            // ---- block t = first half of frame t + second half of frame t - 1 (the carry); the
-            //      rows hold window / 512 / sum(window^2) x the back-scale of the spectra ----
-            const mc::f4 s0 = synr[lane], s1 = synr[64 + lane];
             float blk[4];
 #pragma unroll
-            for (int r = 0; r < 4; ++r) blk[r] = fmaf(y0[r], s0[r] * isc, carry[r]);
+            for (int r = 0; r < 4; ++r) blk[r] = fmaf(y0[k][r], s0[r] * isc[k], carry[r]);
             if (t == 0) {  // no frame before the first: a single contribution (center = False only)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) blk[r] *= gptr(a.mc_edge)[r * 64 + lane];
@@ -474,7 +488,7 @@ __global__ __launch_bounds__(p2mc_threads(PCM), kP2McWavesPerSimd) void beamform
                 }
             }
 #pragma unroll
-            for (int r = 0; r < 4; ++r) carry[r] = y1[r] * (s1[r] * isc);
+            for (int r = 0; r < 4; ++r) carry[r] = y1[k][r] * (s1[r] * isc[k]);
         }
     }
     // ---- the block after the last frame: its second half alone (center = False only) ----
