@@ -45,9 +45,10 @@ def build_library(force=False, verbose=False):
         return _build_locked(force, verbose)
 
 
-def _build_locked(force, verbose):
-    hdrs = [os.path.normpath(os.path.join(CSRC, h)) for h in HEADERS]
-    flags = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast",
+def unit_flags(src, arch=ARCH):
+    """The hipcc flags of one translation unit (everything but -c / -o): what the build uses and
+    what tools/isa_census.py compiles with."""
+    flags = ["--offload-arch=" + arch, "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast",
              # SLP packing into v_pk_* costs more moves than it saves here (measured:
              # stft_covar 2.27 -> 1.86 ms, beamform_istft 1.46 -> 1.30 ms)
              "-fno-slp-vectorize",
@@ -80,6 +81,13 @@ def _build_locked(force, verbose):
     # under both (diffed); cgmm.hip / cgmm_k.hip do not (float64 builtins lose the contract flag), so
     # the switch stays per unit.
     honor = {"solve.hip", "modular.hip"}
+    fl = [f if f != "-ffp-contract=fast" or src not in honor else "-ffp-contract=fast-honor-pragmas"
+          for f in flags]
+    return fl + extra.get(src, [])
+
+
+def _build_locked(force, verbose):
+    hdrs = [os.path.normpath(os.path.join(CSRC, h)) for h in HEADERS]
     jobs = []
     objs = []
     for src in SOURCES:
@@ -87,9 +95,7 @@ def _build_locked(force, verbose):
         o = os.path.join(OBJ, src.replace(".hip", ".o"))
         objs.append(o)
         if force or _stale(o, [s] + hdrs):
-            fl = [f if f != "-ffp-contract=fast" or src not in honor else "-ffp-contract=fast-honor-pragmas"
-                  for f in flags]
-            jobs.append([_hipcc()] + fl + extra.get(src, []) + ["-c", s, "-o", o])
+            jobs.append([_hipcc()] + unit_flags(src) + ["-c", s, "-o", o])
 
     def run(cmd):
         if verbose:

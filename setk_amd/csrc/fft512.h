@@ -280,25 +280,38 @@ template <> struct RawPair<const float*> {
     static SETK_DEV cf get(ptr p, int i) { return p[i]; }
 };
 
-template <class FloatPtr>
+// The frame of every lane of the wavefront is interior in the steady state, so that case is a
+// wave-uniform branch of its own: its sixteen loads write the registers and nothing else does.
+// (As one of three per-lane cases the compiler zeroed all 32 registers ahead of the divergent
+// branches, on every call: 32 v_mov_b32 per transform, profiles/no_copies/census.txt.)  A
+// wavefront with an edge, misaligned or invalid frame takes the per-lane path as a whole: its
+// reflect indexing reads the same samples for an interior frame.
+// (WAVE = false keeps the three cases per lane: stft_binmajor_kernel, which loads once per
+// channel step and spills more registers over the extra branch at its 1024-thread budget.)
+template <class FloatPtr, bool WAVE = true>
 SETK_DEV void load_raw(cf (&v)[16], FloatPtr x, int n_samp, int s, int la, bool valid) {
+    if (!WAVE && !valid) {
+#pragma unroll
+        for (int j = 0; j < 16; ++j) v[j] = make_float2(0.f, 0.f);
+        return;
+    }
+    const bool interior = valid && (s >= 0) && (s + kFrame <= n_samp) && ((((uintptr_t)(x + s)) & 7) == 0);
+    if (WAVE ? __builtin_expect(__builtin_amdgcn_ballot_w64(!interior) == 0, 1) : interior) {
+        typename RawPair<FloatPtr>::ptr p = (typename RawPair<FloatPtr>::ptr)(x + s);
+#pragma unroll
+        for (int j = 0; j < 16; ++j) v[j] = RawPair<FloatPtr>::get(p, la + 16 * j);
+        return;
+    }
     if (!valid) {
 #pragma unroll
         for (int j = 0; j < 16; ++j) v[j] = make_float2(0.f, 0.f);
         return;
     }
-    const bool interior = (s >= 0) && (s + kFrame <= n_samp) && ((((uintptr_t)(x + s)) & 7) == 0);
-    if (interior) {
-        typename RawPair<FloatPtr>::ptr p = (typename RawPair<FloatPtr>::ptr)(x + s);
 #pragma unroll
-        for (int j = 0; j < 16; ++j) v[j] = RawPair<FloatPtr>::get(p, la + 16 * j);
-    } else {
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            const int n = la + 16 * j;
-            v[j] = make_float2(x[reflect_index(s + 2 * n, n_samp)],
-                               x[reflect_index(s + 2 * n + 1, n_samp)]);
-        }
+    for (int j = 0; j < 16; ++j) {
+        const int n = la + 16 * j;
+        v[j] = make_float2(x[reflect_index(s + 2 * n, n_samp)],
+                           x[reflect_index(s + 2 * n + 1, n_samp)]);
     }
 }
 
@@ -311,25 +324,25 @@ SETK_DEV void load_raw(cf (&v)[16], FloatPtr x, int n_samp, int s, int la, bool 
 typedef const SETK_GLOBAL short* gcshort_p;
 typedef const SETK_GLOBAL int* gcint_p;
 SETK_DEV void load_raw_pcm(int (&v)[16], gcshort_p x, int n_samp, int s, int la, bool valid) {
+    // (x is 4-byte aligned and s even by construction: channel strides are even, hop and pad too)
+    const bool interior = valid && (s >= 0) && (s + kFrame <= n_samp) && ((((uintptr_t)(x + s)) & 3) == 0);
+    if (__builtin_expect(__builtin_amdgcn_ballot_w64(!interior) == 0, 1)) {  // wave-uniform, see load_raw
+        gcint_p p = (gcint_p)(x + s);
+#pragma unroll
+        for (int j = 0; j < 16; ++j) v[j] = p[la + 16 * j];
+        return;
+    }
     if (!valid) {
 #pragma unroll
         for (int j = 0; j < 16; ++j) v[j] = 0;
         return;
     }
-    // (x is 4-byte aligned and s even by construction: channel strides are even, hop and pad too)
-    const bool interior = (s >= 0) && (s + kFrame <= n_samp) && ((((uintptr_t)(x + s)) & 3) == 0);
-    if (interior) {
-        gcint_p p = (gcint_p)(x + s);
 #pragma unroll
-        for (int j = 0; j < 16; ++j) v[j] = p[la + 16 * j];
-    } else {
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            const int n = la + 16 * j;
-            const int lo = x[reflect_index(s + 2 * n, n_samp)];
-            const int hi = x[reflect_index(s + 2 * n + 1, n_samp)];
-            v[j] = (lo & 0xffff) | (hi << 16);
-        }
+    for (int j = 0; j < 16; ++j) {
+        const int n = la + 16 * j;
+        const int lo = x[reflect_index(s + 2 * n, n_samp)];
+        const int hi = x[reflect_index(s + 2 * n + 1, n_samp)];
+        v[j] = (lo & 0xffff) | (hi << 16);
     }
 }
 SETK_DEV cf unpack_pcm(int v) { return make_float2((float)(short)(v & 0xffff), (float)(v >> 16)); }
@@ -348,7 +361,7 @@ SETK_DEV float qr_partner(float x) {
 // (16 - la) & 15, register 15 - m (lane 0: its own register 16 - m), fetched with
 // two DPP moves instead of an LDS round trip.  Writes X[k], X[256-k] (m < 8) into
 // the slot and X[256] to *nyq.
-template <int ROW, bool WIDE = (ROW % 2 == 0)>
+template <int ROW, bool WIDE = (ROW % 2 == 0), bool PICK_FIRST = true>
 SETK_DEV void qr_stage23(cf* slot, float* nyq, const cf* tw5_row, int la) {
     cf v[16];
     fft256_stage_b_pad<-1, ROW, WIDE>(v, slot, la);
@@ -369,11 +382,16 @@ SETK_DEV void qr_stage23(cf* slot, float* nyq, const cf* tw5_row, int la) {
     for (int m = 0; m < 8; ++m) {
         if (!WIDE && m + 2 < 8) t5[m + 2] = tw5_row[16 * (m + 2)];
         const cf Zk = v[dft16_pos(m)];
-        const cf src = v[dft16_pos(15 - m)];
-        cf Zm = make_float2(qr_partner(src.x), qr_partner(src.y));
+        // lane 0 is its own partner and wants its register 16 - m: chosen BEFORE the exchange
+        // (no other lane reads lane 0), so the exchange's second move feeds the split's adds
+        // directly and the compiler folds it into them as their DPP operand.  (PICK_FIRST =
+        // false chooses after it: stft_binmajor_kernel, which spills two registers more over
+        // the earlier choice at its 1024-thread budget.)
+        const cf oth = v[dft16_pos(15 - m)];
         const cf own = v[dft16_pos((16 - m) & 15)];
-        Zm.x = lane0 ? own.x : Zm.x;
-        Zm.y = lane0 ? own.y : Zm.y;
+        const cf src = PICK_FIRST ? make_float2(lane0 ? own.x : oth.x, lane0 ? own.y : oth.y) : oth;
+        cf Zm = make_float2(qr_partner(src.x), qr_partner(src.y));
+        if (!PICK_FIRST) Zm = make_float2(lane0 ? own.x : Zm.x, lane0 ? own.y : Zm.y);
         cf Xk, Xm;
         rfft_split(Zk, Zm, t5[m], Xk, Xm);
         if (m == 0) {

@@ -338,11 +338,11 @@ __global__ __launch_bounds__(1024, 4) void stft_binmajor_kernel(Pass1Args a, int
     // the loads are issued at the top of each channel step instead)
     for (int c = 0; c < C; ++c) {
         cf v[16];
-        load_raw(v, gptr(ud.audio) + (size_t)c * n_samp, n_samp, s0, la, valid);
+        load_raw<decltype(gptr(ud.audio)), false>(v, gptr(ud.audio) + (size_t)c * n_samp, n_samp, s0, la, valid);
         apply_window<ROW>(v, win_row);
         fft256_stage_a_pad<-1, ROW>(v, slot, tw_row, la);
         __builtin_amdgcn_wave_barrier();
-        qr_stage23<ROW>(slot, xn + grp, tw5_row, la);
+        qr_stage23<ROW, (ROW % 2 == 0), false>(slot, xn + grp, tw5_row, la);
         __syncthreads();
         // 16-byte stores: a lane writes two consecutive frames of one bin, a wave two bins
         {

@@ -208,6 +208,21 @@ __global__ __launch_bounds__(p2mc_threads(PCM), kP2McWavesPerSimd) void beamform
         const auto x = chan(c);
         const int o = 64 * g + c16;
         const int s0 = min(t0, T - 1) * hop - a.g.pad, s1 = min(t0 + 1, T - 1) * hop - a.g.pad + 256;
+        // interior addresses, from three channels up: a wave-uniform base per half frame, opaque so
+        // that it stays in scalar registers, and the lane's unsigned offset.  Left to itself the
+        // compiler folds the lane's part into a 64-bit address per lane, a loop invariant that
+        // the request sites of the channel loop push into scratch; with one or two channels it
+        // does better left to itself (profiles/no_copies/resource_usage.txt).
+        auto base = [&](int s) __attribute__((always_inline)) {
+            auto xs = x + s;
+            if constexpr (C > 2) asm volatile("" : "+s"(xs));
+            return xs;
+        };
+        const auto xa = base(s0), xb = base(s1);
+        auto at = [&](decltype(xa) xs, int s, int k) __attribute__((always_inline)) {
+            if constexpr (C > 2) return xs + ((unsigned)o + (unsigned)k);
+            else return x + (s + o + k);
+        };
         if constexpr (PCM) {
             // first half: what this lane parked at the end of the previous group (or the prefill
             // before the first); the other two: the only samples of the group not seen yet
@@ -219,8 +234,8 @@ __global__ __launch_bounds__(p2mc_threads(PCM), kP2McWavesPerSimd) void beamform
             if (!decltype(edge)::value) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    v[4 + e] = x[s0 + o + 256 + 16 * e];
-                    nr[e] = x[s1 + o + 16 * e];
+                    v[4 + e] = *at(xa, s0, 256 + 16 * e);
+                    nr[e] = *at(xb, s1, 16 * e);
                 }
             } else {
 #pragma unroll
@@ -237,11 +252,11 @@ __global__ __launch_bounds__(p2mc_threads(PCM), kP2McWavesPerSimd) void beamform
                     // first one is the re-read of what the previous group fetched as ITS last
                     // half): a streaming hint keeps them from pushing the halves that WILL be read
                     // again -- the group's last -- out of the XCD's L2
-                    v[e] = __builtin_nontemporal_load(&x[s0 + o + 16 * e]);
-                    v[4 + e] = __builtin_nontemporal_load(&x[s0 + o + 256 + 16 * e]);
+                    v[e] = __builtin_nontemporal_load(at(xa, s0, 16 * e));
+                    v[4 + e] = __builtin_nontemporal_load(at(xa, s0, 256 + 16 * e));
                 }
 #pragma unroll
-                for (int e = 0; e < 4; ++e) v[8 + e] = x[s1 + o + 16 * e];
+                for (int e = 0; e < 4; ++e) v[8 + e] = *at(xb, s1, 16 * e);
             } else {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
@@ -253,63 +268,105 @@ __global__ __launch_bounds__(p2mc_threads(PCM), kP2McWavesPerSimd) void beamform
         }
     };
     mc::f4 yr[R], yi[R];
-    // the pair of transforms of every channel of one group; `nxt` / `nraw` arrive holding the
-    // group (t0, channel 0) and leave holding (t0 + R, channel 0) once request_group has run
+    // the pair of transforms of every channel of one group.  Two sample buffers swap roles from
+    // channel to channel: a channel's pair is transformed out of `cur` in place while the next
+    // channel's samples travel into `nx` (one buffer cost twelve v_mov_b32 per channel to move
+    // the arrivals out of the way of the next request, profiles/no_copies/census.txt).  Buffer a
+    // arrives holding the group (t0, channel 0) and leaves holding (t0 + R, channel 0) once
+    // request_group has run.
     static_assert(R == 2, "the paired transform and the LDS carry are written for groups of two frames");
-    float nxt[12];
-    int nraw[4];  // PCM: the group's last half frame, as loaded
+    // The second buffer is worth its twelve registers where the loop then still fits the 128:
+    // float32 input from five channels up.  With two to four channels and for PCM input (nraw
+    // doubles too) it pushed one to three registers of the prologue into scratch, so those keep
+    // the one buffer (profiles/no_copies/resource_usage.txt).
+    constexpr bool kTwoBuf = !PCM && C >= 5;
+    float buf_a[12], buf_b[12];
+    int nraw_a[4], nraw_b[4];  // PCM: the group's last half frame, as loaded
+    // one channel; `more`: channel c + 1 exists and is requested
+    auto channel = [&](const float (&cur)[12], const int (&craw)[4], float (&nx)[12], int (&nxraw)[4], int t0,
+                       int c, bool more, auto edge) __attribute__((always_inline)) {
+        float x0[8], x1[8];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            x0[e] = cur[e];
+            x0[4 + e] = cur[4 + e];
+            x1[e] = cur[4 + e];
+            if constexpr (PCM) x1[4 + e] = (float)craw[e];
+            else x1[4 + e] = cur[8 + e];
+        }
+        if constexpr (PCM) {
+            // the group's last half frame is the next group's first
+            carry_l[64 * c] = make_uint2(__builtin_amdgcn_perm((unsigned)craw[1], (unsigned)craw[0], 0x05040100u),
+                                         __builtin_amdgcn_perm((unsigned)craw[3], (unsigned)craw[2], 0x05040100u));
+        }
+        // the next channel's twelve samples travel while this pair runs (the next group's
+        // channel 0 is requested after the group: its span decides the path)
+        if (more) load_pair(nx, nxraw, t0, c + 1, edge);
+        mc::f4 zr0, zi0, a16_0, zr1, zi1, a16_1;
+        {
+            asm volatile("" ::: "memory");  // tiles and tables: once per channel and group, not kept
+            const mc::f4 w0 = __builtin_bit_cast(mc::f4, tiles[20 * 64 + lane]);
+            const mc::f4 w1 = __builtin_bit_cast(mc::f4, tiles[21 * 64 + lane]);
+            const float win[8] = {w0[0], w0[1], w0[2], w0[3], w1[0], w1[1], w1[2], w1[3]};
+            mc::forward2_t(x0, x1, win, [&](int i) { return mc::lds_h8(tiles, 12 + i, lane); },
+                           [&](int i) { return __builtin_bit_cast(mc::f4, tiles[(22 + i) * 64 + lane]); },
+                           zr0, zi0, a16_0, zr1, zi1, a16_1);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("" ::: "memory");  // the weights are re-read per group, not kept (64 registers)
+        const cf* wc = wl + c * F;
+        cf w[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) w[r] = wc[32 * r];
+        mc::store_a16(a16g, c, lane, a16_0);
+        mc::store_a16(a16g + 8 * mc::kOddPitch, c, lane, a16_1);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            yr[0][r] = fmaf(zr0[r], w[r].x, fmaf(zi0[r], w[r].y, yr[0][r]));
+            yi[0][r] = fmaf(zi0[r], w[r].x, fmaf(-zr0[r], w[r].y, yi[0][r]));
+            yr[1][r] = fmaf(zr1[r], w[r].x, fmaf(zi1[r], w[r].y, yr[1][r]));
+            yi[1][r] = fmaf(zi1[r], w[r].x, fmaf(-zr1[r], w[r].y, yi[1][r]));
+        }
+        // the fold stays with its channel (an empty statement that claims the sums: with two
+        // channels in one loop body the compiler otherwise sinks this fold below the next
+        // channel's transforms and keeps sixteen spectrum registers alive across them)
+        if constexpr (kTwoBuf) {
+#pragma unroll
+            for (int k = 0; k < R; ++k) {
+                asm volatile("" : "+v"(yr[k][0]), "+v"(yr[k][1]), "+v"(yr[k][2]), "+v"(yr[k][3]),
+                                  "+v"(yi[k][0]), "+v"(yi[k][1]), "+v"(yi[k][2]), "+v"(yi[k][3]));
+            }
+        }
+        // one pair at a time: the scheduler must not pull the next channel's pair in
+        __builtin_amdgcn_sched_barrier(0);
+    };
     auto group = [&](int t0, auto edge) __attribute__((always_inline)) {
 #pragma unroll
         for (int k = 0; k < R; ++k) {
             yr[k] = (mc::f4){0.f, 0.f, 0.f, 0.f};
             yi[k] = (mc::f4){0.f, 0.f, 0.f, 0.f};
         }
+        if constexpr (decltype(edge)::value || !kTwoBuf) {
+            // one buffer, refilled in place: the first and the last group of an utterance (the
+            // reflect indexing of three request sites would cost more registers than the moves),
+            // and every group of the instantiations outside kTwoBuf
 #pragma unroll 1
-        for (int c = 0; c < C; ++c) {
-            float x0[8], x1[8];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                x0[e] = nxt[e];
-                x0[4 + e] = nxt[4 + e];
-                x1[e] = nxt[4 + e];
-                if constexpr (PCM) x1[4 + e] = (float)nraw[e];
-                else x1[4 + e] = nxt[8 + e];
+            for (int c = 0; c < C; ++c) channel(buf_a, nraw_a, buf_a, nraw_a, t0, c, c + 1 < C, edge);
+        } else {
+            // channels two at a time, a -> b -> a; the last one or two stand outside the loop,
+            // so that inside it every channel requests its successor unconditionally
+            int c = 0;
+#pragma unroll 1
+            for (; c + 2 < C; c += 2) {
+                channel(buf_a, nraw_a, buf_b, nraw_b, t0, c, true, edge);
+                channel(buf_b, nraw_b, buf_a, nraw_a, t0, c + 1, true, edge);
             }
-            if constexpr (PCM) {
-                // the group's last half frame is the next group's first
-                carry_l[64 * c] = make_uint2(__builtin_amdgcn_perm((unsigned)nraw[1], (unsigned)nraw[0], 0x05040100u),
-                                             __builtin_amdgcn_perm((unsigned)nraw[3], (unsigned)nraw[2], 0x05040100u));
+            if constexpr (C % 2 == 0) {
+                channel(buf_a, nraw_a, buf_b, nraw_b, t0, c, true, edge);
+                channel(buf_b, nraw_b, buf_a, nraw_a, t0, c + 1, false, edge);
+            } else {
+                channel(buf_a, nraw_a, buf_b, nraw_b, t0, c, false, edge);
             }
-            // the next channel's twelve samples travel while this pair runs (the next group's
-            // channel 0 is requested after the group: its span decides the path)
-            if (c + 1 < C) load_pair(nxt, nraw, t0, c + 1, edge);
-            mc::f4 zr0, zi0, a16_0, zr1, zi1, a16_1;
-            {
-                asm volatile("" ::: "memory");  // tiles and tables: once per channel and group, not kept
-                const mc::f4 w0 = __builtin_bit_cast(mc::f4, tiles[20 * 64 + lane]);
-                const mc::f4 w1 = __builtin_bit_cast(mc::f4, tiles[21 * 64 + lane]);
-                const float win[8] = {w0[0], w0[1], w0[2], w0[3], w1[0], w1[1], w1[2], w1[3]};
-                mc::forward2_t(x0, x1, win, [&](int i) { return mc::lds_h8(tiles, 12 + i, lane); },
-                               [&](int i) { return __builtin_bit_cast(mc::f4, tiles[(22 + i) * 64 + lane]); },
-                               zr0, zi0, a16_0, zr1, zi1, a16_1);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            asm volatile("" ::: "memory");  // the weights are re-read per group, not kept (64 registers)
-            const cf* wc = wl + c * F;
-            cf w[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) w[r] = wc[32 * r];
-            mc::store_a16(a16g, c, lane, a16_0);
-            mc::store_a16(a16g + 8 * mc::kOddPitch, c, lane, a16_1);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                yr[0][r] = fmaf(zr0[r], w[r].x, fmaf(zi0[r], w[r].y, yr[0][r]));
-                yi[0][r] = fmaf(zi0[r], w[r].x, fmaf(-zr0[r], w[r].y, yi[0][r]));
-                yr[1][r] = fmaf(zr1[r], w[r].x, fmaf(zi1[r], w[r].y, yr[1][r]));
-                yi[1][r] = fmaf(zi1[r], w[r].x, fmaf(-zr1[r], w[r].y, yi[1][r]));
-            }
-            // one pair at a time: the scheduler must not pull the next channel's pair in
-            __builtin_amdgcn_sched_barrier(0);
         }
     };
     auto span_is_edge = [&](int t0) {
@@ -317,8 +374,8 @@ __global__ __launch_bounds__(p2mc_threads(PCM), kP2McWavesPerSimd) void beamform
         return lo < 0 || hi > n_samp || t0 + R > T;
     };
     auto request_group = [&](int t0) __attribute__((always_inline)) {
-        if (span_is_edge(t0)) load_pair(nxt, nraw, t0, 0, std::true_type());
-        else load_pair(nxt, nraw, t0, 0, std::false_type());
+        if (span_is_edge(t0)) load_pair(buf_a, nraw_a, t0, 0, std::true_type());
+        else load_pair(buf_a, nraw_a, t0, 0, std::false_type());
     };
     if constexpr (PCM) {
         // the first half of the wave's first frame, every channel: from here on a group reads two
