@@ -470,6 +470,68 @@ int setk_auxiva_batch(setk_handle_t h, int n_utts, int num_channels, const float
                       const int* num_samples, int num_epochs, void* const* wave, int* status,
                       int flags, void* stream);
 
+/* ---- sound source localisation (scripts/sptk/do_ssl.py, libs/ssl.py) ------
+ * One direction of arrival per window of frames, out of the spectrogram, an optional TF mask and
+ * a steer-vector set sv [A][C][F] complex64 (compute_steer_vector.py's A x M x F file).
+ *   SETK_SSL_ML     ml_ssl (libs/ssl.py:12-43): sv normalised over the microphones, delta =
+ *                   sum_m |x|^2 - |sum_m sv conj(x)|^2 / (1 + eps), ll = -log(max(delta, eps))
+ *                   (compression <= 0) or -delta^compression, score[a] = sum_{t,f} mask ll;
+ *                   `norm` first divides x by max(|x|, eps).  The argmax.
+ *   SETK_SSL_SRP    srp_ssl (:46-77): score[a] = sum_{t,f} mask mean_p cos((arg x_l - arg x_r) -
+ *                   (arg sv_l - arg sv_r)) over the n_pairs microphone pairs (l, r) =
+ *                   (pairs[2p], pairs[2p + 1]) (host array), computed on unit phasors (arg 0 = 0 as
+ *                   np.angle has it) without atan2 / cos.  The argmax.
+ *   SETK_SSL_MUSIC  music_ssl (:80-110): score[a] = sum_f |sv^H E_n E_n^H sv| with E_n E_n^H =
+ *                   I - v v^H, v the principal eigenvector (setk_pevd) of the covariance of
+ *                   stft * mask (setk_covar with the mask squared).  The argmin.
+ * ML and SRP compute float32 frame scores S[t][a] once and sum them per window in frame order
+ * (float64); SRP with a single window folds the frames first.  No floating-point atomics: two
+ * runs give the same bits. */
+#define SETK_SSL_ML 0
+#define SETK_SSL_SRP 1
+#define SETK_SSL_MUSIC 2
+typedef struct setk_ssl_opts {
+    int backend;       /* SETK_SSL_*                                            */
+    int n_pairs;       /* SRP: number of microphone pairs                       */
+    const int* pairs;  /* SRP: host array of 2 n_pairs channel indices          */
+    float compression; /* ML: <= 0 selects the logarithm (do_ssl.py passes -1)  */
+    int norm;          /* ML: normalise the observations                        */
+    double eps;        /* ML: do_ssl.py passes float32 eps, ml_ssl's default is 1e-8 */
+} setk_ssl_opts;
+
+/* get_doa (do_ssl.py:30-37) for every window [windows[2w], windows[2w + 1]) of frames (host
+ * array; NULL: the one window [0, num_frames), the offline case, do_ssl.py:94-98; the online
+ * loop :101-112 is one call with its windows).
+ *   spec    [C][T][F] complex64, mask [T][F] float32 or NULL, steer_vector [A][C][F] complex64
+ *   score   [W][A] float64 or NULL, index [W] int32: the lowest index attaining the extremum,
+ *           as np.argmax / np.argmin choose
+ *   status  one int or NULL: MUSIC, the worst setk_pevd status over bins and windows (a bin
+ *           whose covariance is zero has no defined eigenvector); 0 for the other backends
+ * All data pointers host or device.  Any A, T, F; SETK_ERR_UNSUPPORTED outside 1 <= C <= 16. */
+int setk_ssl_scores(setk_handle_t h, const setk_ssl_opts* opts, const float* spec, const float* mask,
+                    const float* steer_vector, int num_doas, int num_channels, int num_frames,
+                    int num_bins, const int* windows, int num_windows, double* score, int* index,
+                    int* status, void* stream);
+
+/* The loop body of run() (do_ssl.py:80-114) for a batch of utterances with the same channel
+ * count and one steer-vector set: STFT into scratch of the handle's arena (one launch for the
+ * batch up to 8 channels, the stand-alone transform per utterance beyond), frame scores,
+ * windows.
+ *   audio[u]       device float32 [C][num_samples[u]]
+ *   mask           NULL, or per utterance a device float32 [T_u][F] array or NULL
+ *   windows        host, the window tables of all utterances one after another;
+ *                  num_windows[u] >= 1 windows belong to utterance u
+ *   index          [sum W] int32, score [sum W][A] float64 or NULL, status [n_utts] or NULL;
+ *                  host or device
+ * The pointer tables and num_samples are HOST arrays of n_utts entries.  Requires the
+ * n_fft = 512 plan and 1 <= C <= 16; the call returns when the work has run.  With
+ * setk_set_profiling the stage times of setk_last_stage_ms are out[0] STFT, out[1] frame scores
+ * (MUSIC: covariances, eigenvectors and scores), out[2] window reduction and arg-extremum. */
+int setk_ssl_batch(setk_handle_t h, const setk_ssl_opts* opts, int n_utts, int num_channels,
+                   const float* const* audio, const int* num_samples, const float* const* mask,
+                   const float* steer_vector, int num_doas, const int* windows, const int* num_windows,
+                   int* index, double* score, int* status, void* stream);
+
 /* ---- fused hot path ------------------------------------------------------
  * The compute body of apply_adaptive_beamformer.py:130-178 for a batch of
  * utterances that share the channel count, in four kernel stages:

@@ -47,6 +47,32 @@ class BatchTaps(ctypes.Structure):
     _fields_ = [("Rs", c_void_p), ("Rn", c_void_p), ("weight", c_void_p), ("maxabs", c_void_p)]
 
 
+SSL_BACKENDS = {"ml": 0, "srp": 1, "music": 2}  # SETK_SSL_*
+
+
+class SslOpts(ctypes.Structure):
+    _fields_ = [("backend", c_int), ("n_pairs", c_int), ("pairs", POINTER(c_int)),
+                ("compression", c_float), ("norm", c_int), ("eps", ctypes.c_double)]
+
+
+def ssl_opts(backend, srp_pair=None, compression=0.0, eps=1e-8, norm=False):
+    """setk_ssl_opts for a backend name; srp_pair is the reference's (left indices, right
+    indices).  The returned structure keeps its pair table alive."""
+    o = SslOpts(backend=SSL_BACKENDS[backend], n_pairs=0, pairs=None, compression=float(compression),
+                norm=1 if norm else 0, eps=float(eps))
+    if backend == "srp":
+        if srp_pair is None:
+            raise ValueError("srp_pair cannot be None, (list, list)")
+        left, right = srp_pair
+        if len(left) != len(right) or not len(left):
+            raise ValueError("srp_pair: two index lists of the same, non-zero length")
+        flat = [int(v) for lr in zip(left, right) for v in lr]
+        o._pairs = (c_int * len(flat))(*flat)
+        o.pairs = ctypes.cast(o._pairs, POINTER(c_int))
+        o.n_pairs = len(left)
+    return o
+
+
 class SetkError(RuntimeError):
     pass
 
@@ -113,7 +139,7 @@ def exported_symbols():
         "setk_pcm16_to_float", "setk_pcm16_to_float_batch", "setk_pcm16_channel_stride", "setk_pcm16_deinterleave_batch", "setk_kaldi_cm_decode_batch", "setk_float_to_pcm16", "setk_ban", "setk_rank1", "setk_beamform", "setk_cgmm_masks", "setk_cgmm_masks_k", "setk_cgmm_masks_k_status",
         "setk_cgmm_masks_batch", "setk_cgmm_estimate_batch", "setk_enhance_batch", "setk_enhance_batch_taps",
         "setk_apply_weights_batch",
-        "setk_directional_feats", "setk_wpe", "setk_wpe_step", "setk_wpe_batch", "setk_wpe_batch_fnt", "setk_wpe_batch_var", "setk_auxiva", "setk_auxiva_batch", "setk_set_profiling",
+        "setk_directional_feats", "setk_wpe", "setk_wpe_step", "setk_wpe_batch", "setk_wpe_batch_fnt", "setk_wpe_batch_var", "setk_auxiva", "setk_auxiva_batch", "setk_ssl_scores", "setk_ssl_batch", "setk_set_profiling",
         "setk_last_stage_ms",
         "setk_comm_unique_id", "setk_comm_create", "setk_comm_allreduce_f64", "setk_comm_barrier",
         "setk_comm_destroy", "setk_comm_last_error", "setk_host_read_payloads"
@@ -220,6 +246,11 @@ def load_library():
     lib.setk_auxiva.argtypes = [H, fp, c_int, c_int, c_int, c_int, fp, fp, c_void_p]
     lib.setk_auxiva_batch.argtypes = [H, c_int, c_int, POINTER(c_void_p), POINTER(c_int), c_int,
                                       POINTER(c_void_p), fp, c_int, c_void_p]
+    lib.setk_ssl_scores.argtypes = [H, POINTER(SslOpts), fp, fp, fp, c_int, c_int, c_int, c_int,
+                                    POINTER(c_int), c_int, fp, fp, fp, c_void_p]
+    lib.setk_ssl_batch.argtypes = [H, POINTER(SslOpts), c_int, c_int, POINTER(c_void_p), POINTER(c_int),
+                                   POINTER(c_void_p), fp, c_int, POINTER(c_int), POINTER(c_int), fp, fp, fp,
+                                   c_void_p]
     lib.setk_directional_feats.argtypes = [H, fp, fp, POINTER(c_int), c_int, c_int, c_int, c_int,
                                            fp, c_void_p]
     lib.setk_apply_weights_batch.argtypes = [
@@ -721,6 +752,38 @@ class Context:
         self.check(
             self._lib.setk_auxiva_batch(self._h, n, int(C), A, NS, int(num_epochs), W, _ptr(status),
                                         int(flags), current_stream_ptr() if stream is None else stream))
+
+    def ssl_scores(self, opts, spec, mask, sv, A, C, T, F, windows, score, index, status=None, stream=None):
+        """get_doa of do_ssl.py:30-37 per window: spec [C][T][F] complex64, mask [T][F] float32 or
+        None, sv [A][C][F] complex64 (numpy or device tensors); windows a list of (t0, t1) or None
+        (the whole utterance); score float64 [W][A] or None, index int32 [W], status int32[1] or
+        None (numpy or device addresses)."""
+        W = None
+        if windows is not None:
+            flat = [int(v) for w in windows for v in w]
+            W = (c_int * len(flat))(*flat)
+        self.check(
+            self._lib.setk_ssl_scores(self._h, ctypes.byref(opts), _ptr(spec), _ptr(mask), _ptr(sv), int(A),
+                                      int(C), int(T), int(F), W, len(windows) if windows is not None else 1,
+                                      _ptr(score), _ptr(index), _ptr(status),
+                                      current_stream_ptr() if stream is None else stream))
+
+    def ssl_batch(self, opts, C, audio_ptrs, num_samples, mask_ptrs, sv, A, windows, index, score=None,
+                  status=None, stream=None):
+        """Audio in, one direction index per window out: audio / mask device addresses (mask_ptrs
+        None or a list with None entries), windows a list (per utterance) of lists of (t0, t1);
+        index int32 [sum W], score float64 [sum W][A] or None, status int32 [n] or None."""
+        n = len(audio_ptrs)
+        AP = (c_void_p * n)(*audio_ptrs)
+        NS = (c_int * n)(*[int(v) for v in num_samples])
+        MP = (c_void_p * n)(*mask_ptrs) if mask_ptrs is not None else None
+        flat = [int(v) for ws in windows for w in ws for v in w]
+        WT = (c_int * len(flat))(*flat)
+        NW = (c_int * n)(*[len(ws) for ws in windows])
+        self.check(
+            self._lib.setk_ssl_batch(self._h, ctypes.byref(opts), n, int(C), AP, NS, MP, _ptr(sv), int(A), WT, NW,
+                                     _ptr(index), _ptr(score), _ptr(status),
+                                     current_stream_ptr() if stream is None else stream))
 
     def set_profiling(self, on):
         self.check(self._lib.setk_set_profiling(self._h, 1 if on else 0))

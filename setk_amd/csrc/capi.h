@@ -106,6 +106,10 @@ void arena_reset(setk_handle_t h, hipStream_t s);
 int begin_call(setk_handle_t h, void* stream, hipStream_t* s);
 void* arena_alloc(setk_handle_t h, size_t bytes);  // null when the device is out of memory
 int arena_bytes(setk_handle_t h, size_t bytes, void** out, const char* what);
+// hand scratch back inside a call: everything allocated since the mark (in-order stream; see
+// capi_support.hip)
+std::vector<size_t> arena_mark(setk_handle_t h);
+void arena_rewind(setk_handle_t h, const std::vector<size_t>& mark);
 
 // `bytes` of arena as a T*, or SETK_ERR_NOMEM
 template <typename T>
@@ -218,6 +222,11 @@ int carve_wave_f32(setk_handle_t h, std::vector<UttDesc>& uds, void* const* wave
 // them: the kind's range, the caller's own operand check (`own`: its message, null when it
 // passed; `own_code`), MPDR + BAN, PMWF's reference channel against C.
 int check_bf_opts(setk_handle_t h, const setk_bf_opts& o, int C, int own_code, const char* own);
+
+// setk_pevd (Rn NULL) inside another entry point: operands and results are device memory of the
+// running call, whose arena is kept (capi_modular.hip)
+int pevd_in_arena(setk_handle_t h, const float* d_Rs, int F, int C, float* d_pvec, int* d_status,
+                  hipStream_t s);
 
 // ---- stage events of a profiled call (setk_set_profiling / setk_last_stage_ms) ----
 int profile_begin(setk_handle_t h, hipStream_t s);          // five events, the first recorded

@@ -14,7 +14,7 @@ int pitch_of(int F) { return (F == kBins) ? kBinsPad : ((F + 7) / 8) * 8; }
 // the caller has selected the device; the arena is recycled here
 int run_weights(setk_handle_t h, const setk_bf_opts& o, int kind, const float* Rs, const float* Rn,
                 const float* Ry, int F, int C_in, float* weight, int* status, int* ref_out,
-                hipStream_t s) {
+                hipStream_t s, bool reset = true) {
     // 8 < C <= 16: embedded in 16 x 16 problems, blkdiag(Rs, 0) / blkdiag(Rn, max diag(Rn) I):
     // same solution in the first C components, 16 lanes per problem (solve.hip)
     const int C = C_in > kMaxChannels ? kMaxChannels16 : C_in;
@@ -22,7 +22,7 @@ int run_weights(setk_handle_t h, const setk_bf_opts& o, int kind, const float* R
     const int pitch = pitch_of(F);
     const bool mpdr = (kind == SETK_BF_MPDR || kind == SETK_BF_MPDR_WHITEN);
     const int planes = mpdr ? 6 * NP : (Rn ? 4 * NP : 2 * NP);
-    arena_reset(h, s);
+    if (reset) arena_reset(h, s);
     const float *d_Rs, *d_Rn = nullptr, *d_Ry = nullptr;
     const size_t nmat = (size_t)F * C_in * C_in * 2;
     SETK_TRY(stage_in(h, Rs, nmat, s, &d_Rs));
@@ -78,6 +78,15 @@ int run_weights(setk_handle_t h, const setk_bf_opts& o, int kind, const float* R
 }
 
 }  // namespace
+
+namespace setk {
+int pevd_in_arena(setk_handle_t h, const float* d_Rs, int F, int C, float* d_pvec, int* d_status,
+                  hipStream_t s) {
+    setk_bf_opts o;
+    memset(&o, 0, sizeof(o));
+    return run_weights(h, o, kKindPevd, d_Rs, nullptr, nullptr, F, C, d_pvec, d_status, nullptr, s, false);
+}
+}  // namespace setk
 
 extern "C" {
 

@@ -58,6 +58,19 @@ void* arena_alloc(setk_handle_t h, size_t bytes) {
     return nb.ptr;
 }
 
+// Scratch handed back INSIDE a call (a host loop whose steps need the same scratch): the bump
+// offsets are restored, blocks that came later are emptied, nothing is freed.  Safe because a
+// call's launches and copies run in order on its one stream: what reuses the bytes is queued
+// behind what last read them.  Whatever the caller allocated since the mark is gone with it.
+std::vector<size_t> arena_mark(setk_handle_t h) {
+    std::vector<size_t> m;
+    for (auto& b : h->blocks) m.push_back(b.off);
+    return m;
+}
+void arena_rewind(setk_handle_t h, const std::vector<size_t>& m) {
+    for (size_t i = 0; i < h->blocks.size(); ++i) h->blocks[i].off = i < m.size() ? m[i] : 0;
+}
+
 int arena_bytes(setk_handle_t h, size_t bytes, void** out, const char* what) {
     *out = arena_alloc(h, bytes);
     return *out ? SETK_OK : fail(h, SETK_ERR_NOMEM, what);

@@ -269,4 +269,44 @@ hipError_t launch_auxiva_transpose(const float* in, int C, int T, int F, int Tp,
 hipError_t launch_auxiva_spread_norm(const unsigned* norm_bits, int C, int n, unsigned* out,
                                      hipStream_t s);
 
+// Sound source localisation (ssl.hip).  Frame scores S [T][A] float32 out of observations
+// prepared per tile of kSslTile frames (xt: [tiles][F][K][32] complex64, K = channels (ML) or
+// pairs (SRP); pm: [tiles][F][2][32] float32, ML only) and steer-vector operands laid out
+// direction-fastest ([F][K][ssl_apad(A)] complex64); scores per window float64 [W][A].
+constexpr int kSslMl = 0, kSslSrp = 1, kSslMusic = 2;  // = SETK_SSL_*
+constexpr int kSslTile = 32;
+struct SslUtt {         // one utterance of a prep / fold / frame-score launch
+    const float* spec;  // [C][T][pitch] complex64
+    const float* mask;  // [T][F] or null
+    float* xt;          // [tiles][F][K][32] float2: x (ML, normalised when asked) / mask x u_p (SRP)
+    float* pm;          // ML: [tiles][F][2][32]: sum_m |x|^2 | mask.  SRP fold: its partial sums,
+                        // float64 [chunks][P][F][2]
+    float* S;           // [T][A]
+    int T, pitch;
+    int t0, t1;         // SRP fold: the frames summed
+};
+struct SslWin {         // one window of the reduction
+    const float* S;     // [T][A] of the window's utterance (null: the scores are already there)
+    int t0, t1;
+};
+int ssl_apad(int A);
+int ssl_tiles(int T);
+size_t ssl_xt_bytes(int T, int F, int K);
+size_t ssl_pm_bytes(int T, int F);
+size_t ssl_fold_bytes(int frames, int F, int P);  // SRP fold: the partial sums (SslUtt::pm)
+hipError_t launch_ssl_sv_prep(const float* sv, const int* d_pairs, int mode, int A, int C, int F, int K,
+                              float* out, hipStream_t s);
+hipError_t launch_ssl_obs_prep(const SslUtt* d_utts, const int* d_pairs, int mode, int n_utts, int max_frames, int C,
+                               int F, int K, int norm, float eps, hipStream_t s);
+hipError_t launch_ssl_srp_fold(const SslUtt* d_utts, const int* d_pairs, int n_utts, int max_frames, int F, int P,
+                               hipStream_t s);
+hipError_t launch_ssl_frame_scores(const SslUtt* d_utts, const float* svt, int mode, int n_utts, int max_frames, int A,
+                                   int F, int K, float inv1pe, float eps, float compression, hipStream_t s);
+hipError_t launch_ssl_music_prep(const float* spec, const float* mask, int C, int T, int F, int pitch, int t0, int t1,
+                                 float* xo, float* m2, hipStream_t s);
+hipError_t launch_ssl_music_score(const float* svt, const float* v, int A, int F, int C, double* score,
+                                  hipStream_t s);
+hipError_t launch_ssl_windows(const SslWin* d_wins, int n_wins, int A, bool take_min, double* score, int* index,
+                              hipStream_t s);
+
 }  // namespace setk
