@@ -22,7 +22,7 @@ import numpy as np
 from .. import _ffi
 from .._ffi import SetkUnsupported
 from setk_amd.dist import Shard
-from setk_amd.engine import BatchSeparator, Pcm16Frames, _channels_and_size
+from setk_amd.engine import BatchSeparator, Pcm16Frames, channels_and_size
 from setk_amd.libs.data_handler import WaveReader, WaveWriter
 from setk_amd.libs.opts import StftParser
 from setk_amd.libs.utils import get_logger
@@ -81,7 +81,7 @@ def run(args):
             done = 0
             groups = {}
             for key, samps in pending:
-                groups.setdefault(_channels_and_size(samps)[0], []).append((key, samps))
+                groups.setdefault(channels_and_size(samps)[0], []).append((key, samps))
             for nch, items in groups.items():
                 if nch > MAX_CHANNELS:
                     for key, _ in items:

@@ -425,6 +425,33 @@ def test_consumers_fixed_beamformer_and_directional_feats(tmp_path):
     assert wav.shape == ref.shape and rms(wav, ref) / rms(ref) < 1e-3
 
 
+def test_consumers_more_than_eight_channels():
+    """9 channels, 4000 samples: FixedBatchBeamformer leaves the fused batch call for the
+    stand-alone operators, BatchDirectionalFeatures for the mirrored ones; against the oracle at
+    the bounds the other transform size is held to above."""
+    from setk_amd.engine import BatchDirectionalFeatures, FixedBatchBeamformer, Pcm16Frames
+    kw = dict(frame_len=512, frame_hop=256, center=True, window="hann")
+    q = np.round(o.synth_utterance(77, 9, 4000) * 32768.0 * 0.5).astype(np.int16)
+    samps = q.astype(np.float32) / np.float32(32768)
+    obs = np.stack([o.forward_stft(c, round_power_of_two=True, transpose=False, **kw) for c in samps])
+    rng = np.random.default_rng(10)
+    w = ((rng.standard_normal((2, 257, 9)) + 1j * rng.standard_normal((2, 257, 9))) / 9).astype(np.complex64)
+    ref = o.inverse_stft(o.beamform(w[1], obs), norm=float(np.max(np.abs(samps))), transpose=False, **kw)
+    eng = FixedBatchBeamformer(w, **kw)
+    for wav in eng.run([(samps, 1), (Pcm16Frames(np.ascontiguousarray(q.T)), 1)]):
+        assert wav.shape == ref.shape and wav.dtype == np.float32
+        print(f"fixed beamformer, 9 channels: {rms(wav, ref) / rms(ref):.3e}")
+        assert rms(wav, ref) / rms(ref) < 1e-3
+    eng.close()
+    pairs = [(0, 8), (3, 5)]
+    mask = rng.uniform(0.1, 0.9, size=(obs.shape[2], 257)).astype(np.float32)
+    (feats, code), = BatchDirectionalFeatures(pairs, **kw).run([(Pcm16Frames(np.ascontiguousarray(q.T)), mask)])
+    sv = o.solve_pevd(o.compute_covar(obs, mask), gauge=True)
+    dev = np.max(np.abs(feats - o.directional_feats(obs, sv.T, df_pair=pairs)))
+    print(f"directional features, 9 channels: {dev:.3e}")
+    assert code == 0 and feats.dtype == np.float32 and dev < 2e-3
+
+
 def test_streaming_pipeline_equals_batch_path(tmp_path):
     """The streaming host pipeline (pinned slabs, payloads read as stored, batched
     device ingest, several batches in flight) writes the same wavs as the

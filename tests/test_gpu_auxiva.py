@@ -26,18 +26,18 @@ pytestmark = pytest.mark.gpu
 STFT_KW = dict(frame_len=512, frame_hop=256, window="hann", center=True)
 
 
-def spectrogram(samps):
+def spectrogram(samps, kw=STFT_KW):
     """C x N float32 -> the oracle's N x T x F complex64 (SpectrogramReader with transpose)."""
-    return np.stack([o.forward_stft(c, transpose=True, **STFT_KW) for c in np.atleast_2d(samps)])
+    return np.stack([o.forward_stft(c, transpose=True, **kw) for c in np.atleast_2d(samps)])
 
 
-def model_waves(samps, epochs):
+def model_waves(samps, epochs, kw=STFT_KW):
     """run() of the reference on one utterance, with the model in place of auxiva():
     inverse_stft(Y[n], norm=max |samps|) per source (apply_auxiva.py:73-77)."""
     samps = np.atleast_2d(samps)
-    Y = auxiva_model.auxiva(spectrogram(samps), epochs)
+    Y = auxiva_model.auxiva(spectrogram(samps, kw), epochs)
     norm = float(np.max(np.abs(samps)))
-    return np.stack([o.inverse_stft(y, transpose=True, norm=norm, **STFT_KW) for y in Y])
+    return np.stack([o.inverse_stft(y, transpose=True, norm=norm, **kw) for y in Y])
 
 
 def egs_samples():
@@ -171,6 +171,32 @@ def test_engine_matches_model_and_is_reproducible(C):
             dev = pcm16_rel_rms(i16[n], ref[n])
             print(f"engine PCM16 C={C} utt {k} source {n}: {dev:.3e}")
             assert dev <= 1e-3, (C, k, n, dev)
+
+
+def test_engine_other_transform_size_through_the_operators():
+    """n_fft != 512: BatchSeparator runs setk_stft -> setk_auxiva -> setk_istft per utterance on
+    host arrays.  2 channels, 4000 samples, frame 256 / hop 128, float and 16-bit frames in, float
+    and PCM16 out, against the model at the bound of the batched path (1e-3 per source)."""
+    from setk_amd.engine import BatchSeparator, Pcm16Frames
+    kw = dict(STFT_KW, frame_len=256, frame_hop=128)
+    s = auxiva_model.synth_scene(61, 2, 4000)
+    q = np.rint(s * 32767.0).astype(np.int16)
+    sq = q.astype(np.float32) / np.float32(32768.0)
+    eng = BatchSeparator(num_epochs=EPOCHS, **kw)
+    outs = eng.run([s, Pcm16Frames(np.ascontiguousarray(q.T))])
+    assert eng.status == [0, 0]
+    for name, got, ref in zip(("float", "frames"), outs, (model_waves(s, EPOCHS, kw), model_waves(sq, EPOCHS, kw))):
+        assert got.shape == ref.shape and got.dtype == np.float32
+        for n in range(2):
+            dev = rel_rms(got[n], ref[n])
+            print(f"engine, operators path, {name} in, source {n}: {dev:.3e}")
+            assert dev <= 1e-3, (name, n, dev)
+    (i16,) = BatchSeparator(num_epochs=EPOCHS, pcm16=True, **kw).run([s])
+    assert i16.dtype == np.int16 and i16.shape == outs[0].shape
+    for n in range(2):
+        dev = pcm16_rel_rms(i16[n], model_waves(s, EPOCHS, kw)[n])
+        print(f"engine, operators path, PCM16 out, source {n}: {dev:.3e}")
+        assert dev <= 1e-3, (n, dev)
 
 
 def test_engine_groups_mixed_channel_counts():

@@ -291,6 +291,36 @@ def test_batch_is_deterministic_and_equals_single():
             eng.close()
 
 
+def test_batch_other_transform_size_through_the_operators():
+    """n_fft != 512: BatchLocalizer runs setk_stft -> setk_ssl_scores per utterance on host arrays.
+    2 channels, 4000 samples, frame 256 / hop 128, online windows, float input with a mask and
+    16-bit frames without: against the stand-alone operator on the oracle's spectrogram, by the
+    checks of the batched path."""
+    from setk_amd.engine import BatchLocalizer, Pcm16Frames
+    kw = dict(DOC_STFT, frame_len=256, frame_hop=128)
+    pcm = np.ascontiguousarray(load_golden("ref_ssl.npz")["c2_pcm"][:, :4000])
+    x = pcm.astype(np.float32) / np.float32(32768.0)
+    X = np.stack([o.forward_stft(c, transpose=True, **kw) for c in x])
+    C, T, F = X.shape
+    assert (C, T, F) == (2, 32, 129)
+    rng = np.random.default_rng(5)
+    sv = np.exp(1j * rng.uniform(-np.pi, np.pi, size=(24, C, F)))
+    mask = rng.uniform(0.1, 1.0, size=(T, F)).astype(np.float32)
+    eng = BatchLocalizer(backend="ml", steer_vector=sv, chunk_len=8, look_back=12, **kw)
+    out = eng.run([x, Pcm16Frames(np.ascontiguousarray(pcm.T))], [mask, None])
+    assert eng.status == [0, 0]
+    wins = eng.windows(T)
+    assert len(wins) == 4
+    for j, m in enumerate((mask, None)):
+        idx, score = spectrum("ml", X, sv, m, None, windows=wins)
+        assert out[j].shape == (len(wins),) and out[j].dtype == np.int64
+        for w in range(len(wins)):
+            check_spectrum(f"operators path, utterance {j}, window {wins[w]}", eng.scores[j][w], score[w])
+            check_index(f"operators path, utterance {j}, window {wins[w]}", out[j][w], idx[w], score[w], False,
+                        allow_close=True)
+    eng.close()
+
+
 def test_device_tensors_through_the_c_abi():
     """setk_ssl_scores and setk_ssl_batch on torch device tensors: same bits as from host arrays."""
     import torch

@@ -281,6 +281,37 @@ def test_batch_dereverb_resident_matches_oracle(hop, window, pcm):
     assert outs2[1] is None and np.array_equal(outs2[0], outs[0])
 
 
+@pytest.mark.parametrize("pcm", [False, True])
+def test_batch_dereverb_other_transform_size_matches_oracle(pcm):
+    """n_fft != 512: BatchDereverb goes through torch tensors and the stand-alone transform
+    (setk_stft per utterance -> setk_wpe_batch -> setk_istft).  2 channels, 4000 and 4300 samples,
+    frame 256 / hop 128, against the oracle at the bound of the resident path."""
+    from setk_amd.engine import BatchDereverb, Pcm16Frames
+    from setk_amd.libs.wavio import float_to_pcm16
+    kw = dict(frame_len=256, frame_hop=128, window="hann", center=True)
+    utts = []
+    for u, N in enumerate((4000, 4300)):
+        mix = o.synth_utterance(320 + u, 2, N)
+        rev = mix.copy()
+        rev[:, 400:] += 0.4 * mix[:, :-400]
+        if pcm:
+            q = np.round(rev * 32768.0 * 0.5).astype(np.int16)
+            utts.append((Pcm16Frames(np.ascontiguousarray(q.T)), q.astype(np.float32) / 32768.0))
+        else:
+            utts.append((rev.astype(np.float32), rev.astype(np.float32)))
+    outs = BatchDereverb(taps=4, delay=2, context=1, num_iters=3, **kw).run([a for a, _ in utts])
+    for (_, samps), got in zip(utts, outs):
+        obs = o.multichannel_stft(samps, transpose=True, **kw)
+        der = o.wpe(np.transpose(obs, (2, 0, 1)), taps=4, delay=2, context=1, num_iters=3)
+        ref = np.stack([o.inverse_stft(s, transpose=True, **kw) for s in np.transpose(der, (1, 2, 0))])
+        assert got.shape == ref.shape and got.dtype == np.float32
+        print(f"dereverb, torch path, {samps.shape[1]} samples: {rel_rms(got, ref):.3e}")
+        assert rel_rms(got, ref) < 1e-4, rel_rms(got, ref)
+    q = BatchDereverb(taps=4, delay=2, context=1, num_iters=3, pcm16=True, **kw).run([a for a, _ in utts])
+    for f32, i16 in zip(outs, q):
+        assert i16.dtype == np.int16 and np.array_equal(i16, float_to_pcm16(f32).T)
+
+
 def test_batch_wpd_resident_engine_matches_oracle():
     """engine.BatchWpd (what apply_wpd.py runs since round 5): samples -> STFT -> 2 x (WPE step,
     CGMM, power- and mask-weighted covariances, MVDR, beamformer) -> inverse STFT + renorm, on
