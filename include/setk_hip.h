@@ -356,6 +356,44 @@ int setk_cgmm_estimate_batch(setk_handle_t h, int n_utts, int num_channels,
                              const float* const* init_mask, float* const* mask_out, int flags,
                              void* stream);
 
+/* ---- CACGMM mask estimation ---------------------------------------------------
+ * CacgmmTrainer(obs, K, gamma=gamma0, cgmm_init, update_alpha).train(num_iters) of
+ * scripts/sptk/libs/cluster.py:468-535 as used by estimate_cacgmm_masks.py:31-66: the complex
+ * angular central Gaussian mixture on the normalised observation z = x / max(||x||, eps)
+ * (norm_observation, :39-45), Cacgmm.update / predict (:352-393), CacgDistribution
+ * (:298-337), Covariance (:94-135).  One launch runs the start, every iteration and the closing
+ * posterior of every bin, float64 throughout (z too: the reference normalises in complex64).
+ * spec[C][T][F] complex64, 1 <= C <= 8, 2 <= K <= 4 (otherwise SETK_ERR_UNSUPPORTED).
+ * gamma0[K][F][T] float64 is the start (:509-515): an initial mask, or the reference's
+ * np.random.uniform(size=[K, F, T]) / sum over K from the legacy global generator that
+ * estimate_cacgmm_masks.py:28 seeds with --seed; the caller draws it (setk_amd/libs/cluster.py).
+ * gamma0 = NULL needs SETK_CACGMM_CGMM_INIT, otherwise SETK_ERR_INVALID.
+ * gamma_out[K][T][F] float32 receives every class's posteriors (num_iters = 0: the start).
+ * status[F] (host or device, may be NULL) receives the worst SETK_NUM_* of the bin over classes
+ * and iterations: what np.linalg.eigh refuses (:104) -- SETK_NUM_NONFINITE for NaN / inf in the
+ * bin's input or covariance, SETK_NUM_NOCONV when the Jacobi sweep limit was reached.  The
+ * posteriors are written either way.  The environment variable SETK_CACGMM_STREAMING=1 (read at
+ * call time) keeps the bin out of LDS as for an utterance too long to fit: the same bits. */
+#define SETK_CACGMM_UPDATE_ALPHA 0x1 /* --update-alpha: alpha_k = mean_t gamma_k in every M-step
+                                       (Cacgmm.update, cluster.py:364-365) instead of 1 / K */
+#define SETK_CACGMM_CGMM_INIT 0x2    /* --cgmm-init: B_0 = sum_t z z^H / T, B_1 = I, one E-step
+                                       (cluster.py:496-507); K = 2 and gamma0 = NULL only */
+int setk_cacgmm_masks(setk_handle_t h, const float* spec, int num_channels, int num_frames,
+                      int num_bins, int num_classes, int num_iters, const double* gamma0, int flags,
+                      float* gamma_out, int* status, void* stream);
+
+/* The compute loop of estimate_cacgmm_masks.py:31-66 for a batch, audio in, masks out: one STFT
+ * launch (n_fft = 512 plan) straight into the bin-major layout, one EM launch.  Device pointers:
+ * audio[u] float32 [C][num_samples[u]] (16-bit PCM is converted in front, as for
+ * setk_cgmm_estimate_batch: setk_pcm16_to_float_batch), gamma0[u] float64 [K][257][T_u] (the
+ * table may be NULL with SETK_CACGMM_CGMM_INIT), gamma_out[u] float32 [K][T_u][257].  status[u]
+ * (host memory, may be NULL) receives the worst SETK_NUM_* over the bins of utterance u; the call
+ * then returns after the stream has drained. */
+int setk_cacgmm_estimate_batch(setk_handle_t h, int n_utts, int num_channels,
+                               const float* const* audio, const int* num_samples, int num_classes,
+                               int num_iters, const double* const* gamma0, int flags,
+                               float* const* gamma_out, int* status, void* stream);
+
 /* directional_feats (libs/spatial.py:184-208, compute_df_on_mask.py:40-54):
  * out[t][f] = mean over the n_pairs microphone pairs (i, j) = (pairs[2p],
  * pairs[2p+1], host array) of cos((arg X_i - arg X_j) - (arg v_i - arg v_j)),

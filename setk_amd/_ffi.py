@@ -36,6 +36,12 @@ FLAG_NO_RENORM = 32
 FLAG_STRICT_REFERENCE = 64  # numpy.linalg.solve's exact-zero-pivot refusals (setk_hip.h)
 FLAG_IN_PCM16 = 128  # enhance_batch: audio[u] is planar int16 [C][pcm16_channel_stride(N)]
 CGMM_UPDATE_ALPHA = 1
+CACGMM_UPDATE_ALPHA = 1
+CACGMM_CGMM_INIT = 2
+
+
+def cacgmm_flags(update_alpha, cgmm_init):
+    return (CACGMM_UPDATE_ALPHA if update_alpha else 0) | (CACGMM_CGMM_INIT if cgmm_init else 0)
 
 
 class BfOpts(ctypes.Structure):
@@ -137,7 +143,7 @@ def exported_symbols():
         "setk_stft_plan", "setk_stft_num_frames", "setk_istft_num_samples",
         "setk_stft", "setk_stft_batch", "setk_istft", "setk_covar", "setk_pevd", "setk_weights",
         "setk_pcm16_to_float", "setk_pcm16_to_float_batch", "setk_pcm16_channel_stride", "setk_pcm16_deinterleave_batch", "setk_kaldi_cm_decode_batch", "setk_float_to_pcm16", "setk_ban", "setk_rank1", "setk_beamform", "setk_cgmm_masks", "setk_cgmm_masks_k", "setk_cgmm_masks_k_status",
-        "setk_cgmm_masks_batch", "setk_cgmm_estimate_batch", "setk_enhance_batch", "setk_enhance_batch_taps",
+        "setk_cgmm_masks_batch", "setk_cgmm_estimate_batch", "setk_cacgmm_masks", "setk_cacgmm_estimate_batch", "setk_enhance_batch", "setk_enhance_batch_taps",
         "setk_apply_weights_batch",
         "setk_directional_feats", "setk_wpe", "setk_wpe_step", "setk_wpe_batch", "setk_wpe_batch_fnt", "setk_wpe_batch_var", "setk_auxiva", "setk_auxiva_batch", "setk_ssl_scores", "setk_ssl_batch", "setk_set_profiling",
         "setk_last_stage_ms",
@@ -224,6 +230,10 @@ def load_library():
     lib.setk_cgmm_estimate_batch.argtypes = [H, c_int, c_int, POINTER(c_void_p), POINTER(c_int),
                                              c_int, POINTER(c_void_p), POINTER(c_void_p), c_int,
                                              c_void_p]
+    lib.setk_cacgmm_masks.argtypes = [H, fp, c_int, c_int, c_int, c_int, c_int, fp, c_int, fp, fp, c_void_p]
+    lib.setk_cacgmm_estimate_batch.argtypes = [H, c_int, c_int, POINTER(c_void_p), POINTER(c_int), c_int,
+                                               c_int, POINTER(c_void_p), c_int, POINTER(c_void_p),
+                                               POINTER(c_int), c_void_p]
     lib.setk_enhance_batch.argtypes = [
         H, POINTER(BfOpts), c_int, c_int, POINTER(c_void_p), POINTER(c_int),
         POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_int),
@@ -620,6 +630,35 @@ class Context:
             self._lib.setk_cgmm_estimate_batch(self._h, n, int(C), A, NS, int(num_iters), I, O,
                                                CGMM_UPDATE_ALPHA if update_alpha else 0,
                                                current_stream_ptr() if stream is None else stream))
+
+    def cacgmm_masks(self, spec, C, T, F, K, num_iters, gamma0, gamma_out, stream=None,
+                     update_alpha=True, cgmm_init=False, status=None):
+        """CACGMM EM (cluster.py:468-535): spec [C][T][F] complex64, gamma0 [K][F][T] float64 (None
+        with cgmm_init, K = 2), gamma_out [K][T][F] float32; status int32[F] (numpy or device
+        address) or None: SETK_NUM_* per bin (numpy.linalg.eigh's LinAlgError)."""
+        self.check(
+            self._lib.setk_cacgmm_masks(self._h, _ptr(spec), int(C), int(T), int(F), int(K), int(num_iters),
+                                        _ptr(gamma0), cacgmm_flags(update_alpha, cgmm_init),
+                                        _ptr(gamma_out), _ptr(status),
+                                        current_stream_ptr() if stream is None else stream))
+
+    def cacgmm_estimate_batch(self, C, audio_ptrs, num_samples, K, num_iters, gamma0_ptrs, out_ptrs,
+                              stream=None, update_alpha=True, cgmm_init=False, status=None):
+        """audio in, K x T x F masks out: one STFT launch into the bin-major layout, one EM launch.
+        gamma0_ptrs: device addresses of the starts [K][257][T] float64 (None with cgmm_init);
+        status: int32[n] numpy array or None (worst bin of every utterance)."""
+        n = len(audio_ptrs)
+        A = (c_void_p * n)(*audio_ptrs)
+        O = (c_void_p * n)(*out_ptrs)
+        G = (c_void_p * n)(*gamma0_ptrs) if gamma0_ptrs is not None else None
+        NS = (c_int * n)(*[int(v) for v in num_samples])
+        st = (c_int * n)() if status is not None else None
+        self.check(
+            self._lib.setk_cacgmm_estimate_batch(self._h, n, int(C), A, NS, int(K), int(num_iters), G,
+                                                 cacgmm_flags(update_alpha, cgmm_init), O, st,
+                                                 current_stream_ptr() if stream is None else stream))
+        if status is not None:
+            status[:] = list(st)
 
     # -- fused hot path ---------------------------------------------------------
     def enhance_batch(self, opts, num_channels, audio_ptrs, num_samples, mask_ptrs,

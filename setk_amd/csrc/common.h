@@ -253,6 +253,19 @@ size_t wpe_wide_bytes_per_bin(int N, int taps);
 hipError_t launch_wpe_step_batch(const void* d_tbl, int n_utts, int N, int F, int taps,
                                  hipStream_t s);
 
+// CACGMM (cacgmm.hip): one launch runs the whole EM of every (bin, utterance); observations
+// [F][C][Tp] complex64 with Tp = cacgmm_pitch(T), work area cacgmm_work_bytes per utterance
+bool cacgmm_supported(int C, int K);
+const char* cacgmm_limit_message();
+int cacgmm_pitch(int T);
+size_t cacgmm_work_bytes(int K, int T, int F);
+int cacgmm_resident_frames(int C, int max_frames, bool force_streaming);
+size_t cacgmm_args_bytes();
+void cacgmm_fill_args(void* dst, const float* x_bin, const double* gamma0, float* gamma_out, double* work,
+                      int* status, int T);
+hipError_t launch_cacgmm(const void* d_tbl, int n_utts, int C, int F, int K, int num_iters, int flags,
+                         int res_frames, hipStream_t s);
+
 // AuxIVA (auxiva.hip): observations [F][C][Tp] complex64, powers [F][C][Tp] float64 (y as
 // complex64 after the last launch), weights [C][Tp] float64, W [F][C][C] complex128
 bool auxiva_supported(int C);

@@ -8,6 +8,7 @@ from ._common import (BEAMFORMER_KINDS, RANK1, Pcm16Frames, channels_and_size,  
 from .enhance import BatchEnhancer  # noqa: F401
 from .fixed import FixedBatchBeamformer  # noqa: F401
 from .cgmm import CgmmEstimator  # noqa: F401
+from .cacgmm import CacgmmEstimator  # noqa: F401
 from .dereverb import BatchDereverb, BatchWpd  # noqa: F401
 from .auxiva import BatchSeparator  # noqa: F401
 from .ssl import BatchLocalizer  # noqa: F401

@@ -1,5 +1,8 @@
 """
-Mirror of the CGMM part of scripts/sptk/libs/cluster.py (CgmmTrainer, :396-465): K = 2
+Mirror of scripts/sptk/libs/cluster.py: the CGMM part (CgmmTrainer, :396-465) and the CACGMM
+part (norm_observation :39-45, CacgmmTrainer :468-535).
+
+CGMM: K = 2
 classes with the deterministic start or an initial mask (what estimate_cgmm_masks.py uses by
 default: the tuned kernels of csrc/cgmm_bin.hip / cgmm.hip behind setk_cgmm_masks), and
 num_classes 3 or 4 with the reference's random start (csrc/cgmm_k.hip behind
@@ -16,7 +19,17 @@ permu_aligner (:48-91, --solve-permu) is host post-processing of the K x T x F
 posteriors, as in the reference: a per-bin assignment of classes to the running
 centroids of overlapping bands (a few milliseconds of numpy per utterance).
 
-Not mirrored (out of this path's scope): CACGMM, resuming from a pickled model.
+CACGMM (CacgmmTrainer): 2 <= num_classes <= 4 on 1 - 8 channels, the whole EM in one launch of
+csrc/cacgmm.hip behind setk_cacgmm_masks, float64 throughout.  The start is the caller's gamma
+(K x F x T), the reference's random draw (:509-513, for every K, 2 included: the same legacy
+global generator, the same order, drawn here on the host) or, with cgmm_init and K = 2, the
+CGMM-like start (:496-507).  alpha is re-estimated by default (update_alpha), as in the
+reference.  The device normalises the observation in float64, the reference in complex64
+(tests/PARITY_NOTES_CACGMM.md measures the difference); the Q value the reference logs per
+iteration is not computed.
+
+Not mirrored: the classes behind the trainers (Covariance, CgDistribution, Cgmm,
+CacgDistribution, Cacgmm: their arithmetic runs in the kernels), resuming from a pickled model.
 """
 import numpy as np
 
@@ -25,7 +38,7 @@ from .utils import EPSILON, get_logger
 
 logger = get_logger(__name__)
 
-__all__ = ["CgmmTrainer", "permu_aligner"]
+__all__ = ["CgmmTrainer", "CacgmmTrainer", "norm_observation", "permu_aligner"]
 
 
 class CgmmTrainer(object):
@@ -94,6 +107,64 @@ class CgmmTrainer(object):
             bad = int(np.count_nonzero(~np.isfinite(gamma).all(axis=(0, 1))))
             raise np.linalg.LinAlgError(f"Eigenvalues did not converge ({bad} frequency bins with "
                                         "non-finite posteriors)")
+        self.gamma = np.transpose(gamma, (0, 2, 1)).astype(np.float64)
+        return self.gamma
+
+
+def norm_observation(mat, axis=-1, eps=EPSILON):
+    """L2 normalisation of observation vectors (reference :39-45)."""
+    denorm = np.linalg.norm(mat, axis=axis, keepdims=True)
+    return mat / np.maximum(denorm, eps)
+
+
+class CacgmmTrainer(object):
+    """obs: M x F x T complex STFT, gamma: optional start K x F x T.
+    train(num_iters) -> posteriors K x F x T (float64 like the reference)."""
+
+    def __init__(self, obs, num_classes, gamma=None, cacgmm=None, cgmm_init=False, update_alpha=True):
+        if not 2 <= int(num_classes) <= 4:
+            raise _ffi.SetkUnsupported(f"the device CACGMM implements 2 <= num_classes <= 4, got {num_classes}")
+        if cacgmm is not None:
+            raise _ffi.SetkUnsupported("resuming from a pickled cacgmm model is not implemented")
+        self.update_alpha = bool(update_alpha)
+        self.num_classes = K = int(num_classes)
+        M, F, T = obs.shape
+        if not 1 <= M <= 8:
+            raise _ffi.SetkUnsupported(f"the device CACGMM implements 1 - 8 channels, got {M}")
+        logger.info(f"CACGMM instance: F = {F:d}, T = {T:}, M = {M}")
+        self.shape = (M, F, T)
+        self.spec = np.ascontiguousarray(np.transpose(obs, (0, 2, 1)), dtype=np.complex64)
+        # cluster.py:496: the CGMM-like start only with two classes; otherwise it falls through
+        self.cgmm_init = bool(cgmm_init) and K == 2
+        self.gamma0 = None
+        if self.cgmm_init:
+            logger.info("Using cgmm init for num_classes = 2")
+        elif gamma is not None:
+            gamma = np.asarray(gamma, dtype=np.float64)
+            if gamma.shape != (K, F, T):
+                raise ValueError(f"initial gamma must be K x F x T, got {gamma.shape}")
+            self.gamma0 = np.ascontiguousarray(gamma)
+        else:
+            # cluster.py:509-513, from numpy's legacy global generator (seeded by the CLI)
+            g = np.random.uniform(size=[K, F, T])
+            self.gamma0 = np.ascontiguousarray(g / np.sum(g, 0, keepdims=True))
+            logger.info(f"Random initialized, num_classes = {K}")
+        self.gamma = None
+
+    def train(self, num_iters):
+        M, F, T = self.shape
+        K = self.num_classes
+        if not np.isfinite(self.spec.view(np.float32)).all():
+            # the reference's np.linalg.eigh raises on a covariance with NaN / inf (cluster.py:104)
+            raise np.linalg.LinAlgError("Eigenvalues did not converge (non-finite spectrogram)")
+        gamma = np.empty((K, T, F), dtype=np.float32)
+        status = np.zeros(F, dtype=np.int32)
+        _ffi.default_context().cacgmm_masks(self.spec, M, T, F, K, num_iters, self.gamma0, gamma,
+                                            update_alpha=self.update_alpha, cgmm_init=self.cgmm_init,
+                                            status=status)
+        if status.any() or not np.isfinite(gamma).all():
+            raise np.linalg.LinAlgError(f"Eigenvalues did not converge ({int(np.count_nonzero(status))} "
+                                        "frequency bins)")
         self.gamma = np.transpose(gamma, (0, 2, 1)).astype(np.float64)
         return self.gamma
 
