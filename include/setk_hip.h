@@ -570,6 +570,67 @@ int setk_ssl_batch(setk_handle_t h, const setk_ssl_opts* opts, int n_utts, int n
                    const float* steer_vector, int num_doas, const int* windows, const int* num_windows,
                    int* index, double* score, int* status, void* stream);
 
+/* ---- geometry-driven spatial features (scripts/sptk/libs/spatial.py) -------
+ * All kinds start from the pair coherence u_p[t][f] = exp(i (arg X_l - arg X_r)) of the n_pairs
+ * microphone pairs (l, r) = (pairs[2p], pairs[2p + 1]) (host array), computed on unit phasors
+ * (arg 0 = 0, as np.angle has it).  out is float32 [T][width]:
+ *   SETK_SPATIAL_IPD          ipd() (libs/spatial.py:163-176): the phase difference wrapped into
+ *                             [-pi, pi), the pairs side by side (np.hstack,
+ *                             compute_ipd_and_linear_srp.py:36-47); width = n_pairs F
+ *   SETK_SPATIAL_COS_IPD      cos=True (:177-179); width = n_pairs F
+ *   SETK_SPATIAL_COS_SIN_IPD  sin=True (:180-181): [cos | sin] per pair; width = 2 n_pairs F
+ *   SETK_SPATIAL_DF           directional_feats (:184-208) for n_index directions of the
+ *                             steer-vector set sv [num_sv][C][F] complex64 (host or device),
+ *                             laid out as compute_df_on_geometry.py:49-60 does:
+ *                             out[t][k F + f] = mean_p cos((arg X_l - arg X_r) - (arg v_l - arg v_r)),
+ *                             v = sv[doa_index[k]]; width = n_index F
+ *   SETK_SPATIAL_SRP          the SRP-PHAT angular spectrum of gcc_phat_linear / srp_phat_linear
+ *                             (:37-57, :95-123) and gcc_phat_diag (:60-92) averaged as
+ *                             compute_circular_srp.py:40-51 does: per pair s_p[t][d] =
+ *                             Re sum_f u_p[t][f] W_p[f][d], divided by max(max_{t,d} |s_p|,
+ *                             float32 eps), floored at 0, then out[t][d] = sum_p pair_weight[p] x
+ *                             that (the pairs in order); width = num_doas.  The table W_p =
+ *                             exp(-i omega_f tau_{p,d}) is the caller's: [n_pairs][F][Dpad]
+ *                             complex64 (host or device), Dpad = num_doas rounded up to a multiple
+ *                             of 64, zero beyond num_doas; pair_weight is a host array.
+ * Maxima are integer maxima on the bits of non-negative floats: no floating-point atomics, two
+ * runs give the same bits.  2 <= C <= 16, n_pairs <= 120, F >= 2 (otherwise
+ * SETK_ERR_UNSUPPORTED); any T >= 1, any num_doas >= 1. */
+#define SETK_SPATIAL_IPD 0
+#define SETK_SPATIAL_COS_IPD 1
+#define SETK_SPATIAL_COS_SIN_IPD 2
+#define SETK_SPATIAL_DF 3
+#define SETK_SPATIAL_SRP 4
+typedef struct setk_spatial_opts {
+    int kind;                  /* SETK_SPATIAL_*                                        */
+    int n_pairs;               /* number of microphone pairs                            */
+    const int* pairs;          /* host array of 2 n_pairs channel indices               */
+    int num_doas;              /* SRP: directions D of the table                        */
+    const float* table;        /* SRP: W [n_pairs][F][Dpad] complex64                   */
+    const float* pair_weight;  /* SRP: host [n_pairs]                                   */
+    int num_sv;                /* DF: directions of the steer-vector set                */
+    const float* steer_vector; /* DF: [num_sv][C][F] complex64                          */
+    int n_index;               /* DF: directions per utterance                          */
+    const int* doa_index;      /* DF: host [n_utts][n_index], each in [0, num_sv)       */
+} setk_spatial_opts;
+
+/* One spectrogram spec [C][T][F] complex64 -> out [T][width] float32; data pointers host or
+ * device.  With device operands the call is asynchronous, like the other stand-alone operators. */
+int setk_spatial_feats(setk_handle_t h, const setk_spatial_opts* opts, const float* spec,
+                       int num_channels, int num_frames, int num_bins, float* out, void* stream);
+
+/* The loop bodies of compute_ipd_and_linear_srp.py:52-73, compute_circular_srp.py:38-55 and
+ * compute_df_on_geometry.py:47-69 behind the STFT, for a batch of spectrograms of one channel
+ * count: spec[u] device complex64 [C][num_frames[u]][F] (what setk_stft_batch wrote), out[u]
+ * device float32 [num_frames[u]][width]; the pointer tables and num_frames are HOST arrays of
+ * n_utts entries.  One set of launches for the batch (IPD, DF: one; SRP: the observation tiles,
+ * the pair contraction, the combination), scratch from the handle's arena (SRP: per utterance
+ * n_pairs T (F 256 bytes per 32 frames + 4 Dpad bytes)); asynchronous on `stream`.  Each
+ * utterance's result has the bits of setk_spatial_feats on the same spectrogram. */
+int setk_spatial_batch(setk_handle_t h, const setk_spatial_opts* opts, int n_utts, int num_channels,
+                       const float* const* spec, const int* num_frames, int num_bins,
+                       float* const* out, void* stream);
+
 /* ---- fused hot path ------------------------------------------------------
  * The compute body of apply_adaptive_beamformer.py:130-178 for a batch of
  * utterances that share the channel count, in four kernel stages:

@@ -79,6 +79,59 @@ def ssl_opts(backend, srp_pair=None, compression=0.0, eps=1e-8, norm=False):
     return o
 
 
+SPATIAL_KINDS = {"ipd": 0, "cos_ipd": 1, "cos_sin_ipd": 2, "df": 3, "srp": 4}  # SETK_SPATIAL_*
+
+
+class SpatialOpts(ctypes.Structure):
+    _fields_ = [("kind", c_int), ("n_pairs", c_int), ("pairs", POINTER(c_int)), ("num_doas", c_int),
+                ("table", c_void_p), ("pair_weight", POINTER(c_float)), ("num_sv", c_int),
+                ("steer_vector", c_void_p), ("n_index", c_int), ("doa_index", POINTER(c_int))]
+
+
+def spatial_dpad(num_doas):
+    """Row pitch of the SRP table: the directions rounded up to a multiple of 64."""
+    return (int(num_doas) + 63) & ~63
+
+
+def spatial_opts(kind, pairs, table=None, num_doas=0, pair_weight=None, steer_vector=None, num_sv=0,
+                 doa_index=None):
+    """setk_spatial_opts for a kind name.  pairs [(l, r), ...]; SRP: table [P][F][spatial_dpad(D)]
+    complex64 (numpy array or device address) and the weight of every pair; DF: steer_vector
+    [A][C][F] complex64 (numpy array or device address) and doa_index, one list of directions per
+    utterance (all of one length).  The returned structure keeps its host tables alive."""
+    flat = [int(v) for p in pairs for v in p]
+    o = SpatialOpts(kind=SPATIAL_KINDS[kind], n_pairs=len(flat) // 2)
+    o._pairs = (c_int * len(flat))(*flat)
+    o.pairs = ctypes.cast(o._pairs, POINTER(c_int))
+    if kind == "srp":
+        o._table = table
+        o.table = _ptr(table)
+        o.num_doas = int(num_doas)
+        o._weight = (c_float * o.n_pairs)(*[float(w) for w in pair_weight])
+        o.pair_weight = ctypes.cast(o._weight, POINTER(c_float))
+    elif kind == "df":
+        o._sv = steer_vector
+        o.steer_vector = _ptr(steer_vector)
+        o.num_sv = int(num_sv)
+        idx = [[int(v) for v in row] for row in doa_index]
+        if len({len(row) for row in idx}) != 1 or not idx[0]:
+            raise ValueError("doa_index: the same, non-zero number of directions for every utterance")
+        o.n_index = len(idx[0])
+        flat = [v for row in idx for v in row]
+        o._index = (c_int * len(flat))(*flat)
+        o.doa_index = ctypes.cast(o._index, POINTER(c_int))
+    return o
+
+
+def spatial_width(opts, F):
+    """Columns of the feature map of one utterance."""
+    if opts.kind == SPATIAL_KINDS["srp"]:
+        return opts.num_doas
+    if opts.kind == SPATIAL_KINDS["df"]:
+        return opts.n_index * F
+    return (2 if opts.kind == SPATIAL_KINDS["cos_sin_ipd"] else 1) * opts.n_pairs * F
+
+
 class SetkError(RuntimeError):
     pass
 
@@ -145,7 +198,7 @@ def exported_symbols():
         "setk_pcm16_to_float", "setk_pcm16_to_float_batch", "setk_pcm16_channel_stride", "setk_pcm16_deinterleave_batch", "setk_kaldi_cm_decode_batch", "setk_float_to_pcm16", "setk_ban", "setk_rank1", "setk_beamform", "setk_cgmm_masks", "setk_cgmm_masks_k", "setk_cgmm_masks_k_status",
         "setk_cgmm_masks_batch", "setk_cgmm_estimate_batch", "setk_cacgmm_masks", "setk_cacgmm_estimate_batch", "setk_enhance_batch", "setk_enhance_batch_taps",
         "setk_apply_weights_batch",
-        "setk_directional_feats", "setk_wpe", "setk_wpe_step", "setk_wpe_batch", "setk_wpe_batch_fnt", "setk_wpe_batch_var", "setk_auxiva", "setk_auxiva_batch", "setk_ssl_scores", "setk_ssl_batch", "setk_set_profiling",
+        "setk_directional_feats", "setk_wpe", "setk_wpe_step", "setk_wpe_batch", "setk_wpe_batch_fnt", "setk_wpe_batch_var", "setk_auxiva", "setk_auxiva_batch", "setk_ssl_scores", "setk_ssl_batch", "setk_spatial_feats", "setk_spatial_batch", "setk_set_profiling",
         "setk_last_stage_ms",
         "setk_comm_unique_id", "setk_comm_create", "setk_comm_allreduce_f64", "setk_comm_barrier",
         "setk_comm_destroy", "setk_comm_last_error", "setk_host_read_payloads"
@@ -261,6 +314,9 @@ def load_library():
     lib.setk_ssl_batch.argtypes = [H, POINTER(SslOpts), c_int, c_int, POINTER(c_void_p), POINTER(c_int),
                                    POINTER(c_void_p), fp, c_int, POINTER(c_int), POINTER(c_int), fp, fp, fp,
                                    c_void_p]
+    lib.setk_spatial_feats.argtypes = [H, POINTER(SpatialOpts), fp, c_int, c_int, c_int, fp, c_void_p]
+    lib.setk_spatial_batch.argtypes = [H, POINTER(SpatialOpts), c_int, c_int, POINTER(c_void_p), POINTER(c_int),
+                                       c_int, POINTER(c_void_p), c_void_p]
     lib.setk_directional_feats.argtypes = [H, fp, fp, POINTER(c_int), c_int, c_int, c_int, c_int,
                                            fp, c_void_p]
     lib.setk_apply_weights_batch.argtypes = [
@@ -823,6 +879,23 @@ class Context:
             self._lib.setk_ssl_batch(self._h, ctypes.byref(opts), n, int(C), AP, NS, MP, _ptr(sv), int(A), WT, NW,
                                      _ptr(index), _ptr(score), _ptr(status),
                                      current_stream_ptr() if stream is None else stream))
+
+    def spatial_feats(self, opts, spec, C, T, F, out, stream=None):
+        """One spectrogram spec [C][T][F] complex64 -> out [T][spatial_width(opts, F)] float32 (numpy
+        arrays, device tensors or device addresses)."""
+        self.check(
+            self._lib.setk_spatial_feats(self._h, ctypes.byref(opts), _ptr(spec), int(C), int(T), int(F),
+                                         _ptr(out), current_stream_ptr() if stream is None else stream))
+
+    def spatial_batch(self, opts, C, spec_ptrs, num_frames, F, out_ptrs, stream=None):
+        """A batch of device spectrograms [C][T_u][F] -> device feature maps, one set of launches."""
+        n = len(spec_ptrs)
+        SP = (c_void_p * n)(*spec_ptrs)
+        OP = (c_void_p * n)(*out_ptrs)
+        NF = (c_int * n)(*[int(t) for t in num_frames])
+        self.check(
+            self._lib.setk_spatial_batch(self._h, ctypes.byref(opts), n, int(C), SP, NF, int(F), OP,
+                                         current_stream_ptr() if stream is None else stream))
 
     def set_profiling(self, on):
         self.check(self._lib.setk_set_profiling(self._h, 1 if on else 0))

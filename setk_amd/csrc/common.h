@@ -322,4 +322,28 @@ hipError_t launch_ssl_music_score(const float* svt, const float* v, int A, int F
 hipError_t launch_ssl_windows(const SslWin* d_wins, int n_wins, int A, bool take_min, double* score, int* index,
                               hipStream_t s);
 
+// Geometry-driven spatial features (spatial.hip): IPD maps, directional features over several
+// directions, SRP-PHAT angular spectra.  All start from the pair coherence u_p = exp(i (arg X_l -
+// arg X_r)).  SRP reads the observations in ssl.hip's tile layout (ssl_obs_prep_kernel<kSslSrp>
+// without a mask) and a table W [P][F][ssl_apad(D)] complex64, direction fastest.
+constexpr int kSpatialIpd = 0, kSpatialCosIpd = 1, kSpatialCosSinIpd = 2, kSpatialDf = 3,
+              kSpatialSrp = 4;  // = SETK_SPATIAL_*
+constexpr int kSpatialMaxPairs = 120;
+struct SpatialUtt {
+    const float* spec;  // [C][T][F] complex64
+    float* out;         // the features, [T][width]
+    float* sp;          // SRP: s_p [P][T][Dpad] float32
+    unsigned* pmax;     // SRP: [P] the bits of max_{t,d} |s_p|
+    int T;
+    int idx0;           // DF: where this utterance's direction indices start
+};
+hipError_t launch_spatial_ipd(const SpatialUtt* d_utts, const int* d_pairs, int kind, int n_utts, int max_frames,
+                              int F, int P, hipStream_t s);
+hipError_t launch_spatial_df(const SpatialUtt* d_utts, const int* d_pairs, const float* sv, const int* d_idx,
+                             int n_idx, int n_utts, int max_frames, int C, int F, int P, hipStream_t s);
+hipError_t launch_spatial_srp_pairs(const SslUtt* d_obs, const SpatialUtt* d_utts, const float* table, int n_utts,
+                                    int max_frames, int D, int F, int P, hipStream_t s);
+hipError_t launch_spatial_srp_combine(const SpatialUtt* d_utts, const float* d_weight, int n_utts, int max_frames,
+                                      int D, int P, hipStream_t s);
+
 }  // namespace setk

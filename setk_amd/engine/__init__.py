@@ -13,3 +13,4 @@ from .dereverb import BatchDereverb, BatchWpd  # noqa: F401
 from .auxiva import BatchSeparator  # noqa: F401
 from .ssl import BatchLocalizer  # noqa: F401
 from .directional import BatchDirectionalFeatures  # noqa: F401
+from .spatial import BatchSpatialFeatures  # noqa: F401

@@ -1,0 +1,155 @@
+"""
+A numpy restatement, in float32, of what spatial.hip computes (setk_amd/csrc/spatial.hip): the
+pair coherence on unit phasors, IPD / cosIPD / sinIPD, the directional features over several
+directions and the SRP-PHAT angular spectrum with the kernel's order of operations for the
+normaliser (max |s_p| over the whole utterance, then max(., eps), one division per cell) and the
+floor.  The bin sums of the contraction run in float32 but not in the kernel's fused
+multiply-add order: the model bounds the arithmetic, it is not a bit-exact twin.
+
+*** TEST INFRASTRUCTURE -- NOT PRODUCT CODE ***
+
+CASES names the operator cases of tests/golden/ref_spatial.npz (tools/make_spatial_golden.py);
+spec_of() turns a stored spectrogram (small integers, int8 [C][T][F][2]) into complex64.
+"""
+import numpy as np
+
+EPS = np.finfo(np.float32).eps
+f32 = np.float32
+
+# name -> (channels, T, F, D, topology or None, samp_doa)
+LINEAR = {
+    "lin4": (4, 37, 33, 181, (0.0, 0.2, 0.4, 0.8), True),
+    "lin2": (2, 1, 33, 7, (0.0, 0.1), True),
+    "lin3": (3, 33, 257, 65, (0.0, 0.05, 0.15), True),
+    "lin8": (8, 40, 257, 181, (0.0, 0.04, 0.08, 0.12, 0.16, 0.2, 0.24, 0.28), True),
+    "lin4_tdoa": (4, 37, 33, 181, (0.0, 0.2, 0.4, 0.8), False),
+}
+CIRCULAR = {"circ6": (6, 37, 257, 121, [(0, 3), (1, 4), (2, 5)], 6, 0.07)}
+IPD_PAIRS = [(0, 1), (3, 1)]
+DF_CASES = {"df_one": ([0], [(0, 1)]), "df_three": ([2, 0, 5], None)}
+SV_TOPO = (0.0, 0.05, 0.1, 0.15)
+SPEC_SEEDS = {"lin4": 1, "lin2": 2, "lin3": 3, "lin8": 4, "circ6": 5}
+
+
+def make_spec(name, C, T, F):
+    """Small integers (|re|, |im| <= 7, zeros included): exact in every format, compressible."""
+    rng = np.random.default_rng(1000 + SPEC_SEEDS[name])
+    return rng.integers(-7, 8, size=(C, T, F, 2)).astype(np.int8)
+
+
+def spec_of(stored):
+    s = np.asarray(stored).astype(np.float32)
+    return np.ascontiguousarray(s[..., 0] + 1j * s[..., 1]).astype(np.complex64)
+
+
+def phasor(x):
+    """exp(i angle(x)) in float32; angle(0) = 0."""
+    x = np.asarray(x, dtype=np.complex64)
+    re, im = x.real.astype(f32), x.imag.astype(f32)
+    n = np.sqrt(re * re + im * im, dtype=f32)
+    r = np.where(n > 0, f32(1) / np.where(n > 0, n, f32(1)), f32(0)).astype(f32)
+    return np.where(n > 0, re * r, f32(1)).astype(f32), np.where(n > 0, im * r, f32(0)).astype(f32)
+
+
+def coherence(xl, xr):
+    """(cos, sin) of arg xl - arg xr."""
+    lr, li = phasor(xl)
+    rr, ri = phasor(xr)
+    return (lr * rr + li * ri).astype(f32), (li * rr - lr * ri).astype(f32)
+
+
+def ipd(S, pairs, cos=False, sin=False):
+    out = []
+    for l, r in pairs:
+        c, s = coherence(S[l], S[r])
+        if not cos:
+            v = np.arctan2(s, c).astype(f32)
+            out.append(np.where(v >= f32(np.pi), v - f32(2) * f32(np.pi), v).astype(f32))
+        elif not sin:
+            out.append(c)
+        else:
+            out += [c, s]
+    return np.hstack(out)
+
+
+def circle_distance(a, b):
+    """Raw IPD is compared on the circle: the reference's range is [-pi, pi) and a rounding at
+    the edge flips the sign."""
+    return np.abs(np.mod(np.asarray(a, np.float64) - np.asarray(b, np.float64) + np.pi, 2 * np.pi) - np.pi)
+
+
+def geometry_df(S, sv, idx, pairs):
+    """S M x T x F, sv A x M x F -> T x (len(idx) F)."""
+    M, T, F = S.shape
+    if pairs is None:
+        pairs = [(i, j) for i in range(M) for j in range(i + 1, M)]
+    out = np.zeros((T, len(idx), F), dtype=f32)
+    for k, a in enumerate(idx):
+        acc = np.zeros((T, F), dtype=f32)
+        for l, r in pairs:
+            c, s = coherence(S[l], S[r])
+            dc, ds = coherence(sv[a, l], sv[a, r])
+            acc = (acc + (c * dc[None] + s * ds[None])).astype(f32)
+        out[:, k] = acc / f32(len(pairs))
+    return out.reshape(T, -1)
+
+
+def linear_grid(dist, num_bins, num_doa, samp_doa=True, sr=16000, speed=343):
+    dist = np.abs(dist)
+    if samp_doa:
+        tau = np.cos(np.linspace(0, np.pi, num_doa)) * dist / speed
+    else:
+        tau = np.linspace(dist / speed, -dist / speed, num_doa)
+    omega = np.linspace(0, sr / 2, num_bins) * 2 * np.pi
+    return np.exp(-1j * np.outer(omega, tau))
+
+
+def diag_grid(angle_delta, d, num_bins, num_doas, sr=16000, speed=343):
+    tau = np.cos(angle_delta - np.linspace(0, np.pi * 2, num_doas)) * d / speed
+    omega = np.linspace(0, sr / 2, num_bins) * 2 * np.pi
+    return np.exp(-1j * np.outer(omega, tau))
+
+
+def srp(S, pairs, grids, weights):
+    """sum_p w_p max(s_p / max(max |s_p|, eps), 0), the grids rounded once to complex64."""
+    out = None
+    for (l, r), g, w in zip(pairs, grids, weights):
+        g = np.asarray(g).astype(np.complex64)
+        c, s = coherence(S[l], S[r])
+        sp = (c @ g.real.astype(f32) - s @ g.imag.astype(f32)).astype(f32)
+        m = np.maximum(np.max(np.abs(sp)), EPS).astype(f32)
+        gcc = np.maximum(sp / m, f32(0)).astype(f32)
+        out = f32(w) * gcc if out is None else (out + f32(w) * gcc).astype(f32)
+    return out
+
+
+def linear_pairs(N):
+    if N == 2:
+        return [(0, 1)], [1.0]
+    pairs = [(i, j) for i in range(N) for j in range(i + 1, N)]
+    return pairs, [2.0 / (N * (N - 1))] * len(pairs)
+
+
+def srp_linear(S, topo, num_doa, samp_doa=True):
+    pairs, w = linear_pairs(S.shape[0])
+    grids = [linear_grid(topo[j] - topo[i], S.shape[2], num_doa, samp_doa) for i, j in pairs]
+    return srp(S, pairs, grids, w)
+
+
+def srp_circular(S, pairs, n, d, num_doas):
+    grids = [diag_grid(min(i, j) * np.pi * 2 / n, d, S.shape[2], num_doas) for i, j in pairs]
+    return srp(S, pairs, grids, [1.0 / len(pairs)] * len(pairs))
+
+
+def e2e_bound(X_ref, E, pairs, norms, weights):
+    """The derived bound of the end-to-end SRP comparison, per frame (T,): a spectrogram that is
+    off by at most E in every bin moves each coherence term by at most e_f = E (1/|X_l| + 1/|X_r|),
+    a pair's row sum by B_p(t) = sum_f e_f and its normaliser by max_t B_p; the factor 2 covers
+    the second order.  norms: the reference's normaliser m_p per pair."""
+    X = np.abs(np.asarray(X_ref)).astype(np.float64)
+    bound = np.zeros(X.shape[1])
+    with np.errstate(divide="ignore"):
+        for (l, r), m, w in zip(pairs, norms, weights):
+            B = (E * (1.0 / X[l] + 1.0 / X[r])).sum(axis=1)
+            bound += w * (B + B.max()) / m
+    return 1e-4 + 2.0 * bound / np.sum(weights)
