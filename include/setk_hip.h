@@ -631,6 +631,76 @@ int setk_spatial_batch(setk_handle_t h, const setk_spatial_opts* opts, int n_utt
                        const float* const* spec, const int* num_frames, int num_bins,
                        float* const* out, void* stream);
 
+/* ---- OM-LSA noise suppression (scripts/sptk/libs/ns.py, apply_ns.py) --------
+ * MCRA.run (libs/ns.py:56-209) and iMCRA.run (:247-387): the spectral gain of the optimally
+ * modified log-spectral amplitude estimator with minima-controlled recursive averaging of the
+ * noise, one channel.  float64 throughout like the reference, the exponential integral of
+ * :65-66 / :259-260 (scipy.integrate.quad per cell there) in closed form.  One workgroup per
+ * utterance walks the frames; the fields are the constructor arguments (:18-54, :221-245) after
+ * the conversions the constructors make. */
+#define SETK_NS_MCRA 0
+#define SETK_NS_IMCRA 1
+#define SETK_NS_OUT_GAIN 0x1 /* the gain, float64 [T][F]                              */
+#define SETK_NS_OUT_SPEC 0x2 /* gain x spectrogram, complex64 [T][F], in the same pass */
+#define SETK_NS_MAX_TAPS 63
+typedef struct setk_ns_opts {
+    int kind;  /* SETK_NS_*                                                          */
+    int flags; /* SETK_NS_OUT_*                                                      */
+    double alpha, alpha_s, alpha_d;
+    double gmin;   /* 10^(gmin_db / 10)                                              */
+    double xi_min; /* 10^(xi_min_db / 10)                                            */
+    /* the smoothing windows as np.convolve takes them: scipy.signal.get_window(h, 2 w + 1),
+     * fftbins=True (periodic: hann, 3 taps is [0, 0.75, 0.75]); host arrays of n_* taps, each odd
+     * and at most SETK_NS_MAX_TAPS.  iMCRA reads w_mcra alone. */
+    int n_mcra, n_local, n_global;
+    const double *w_mcra, *w_local, *w_global;
+    /* MCRA */
+    double delta, beta, alpha_p, q_max;
+    double zeta_min, zeta_max, zeta_p_min, zeta_p_max; /* 10^(*_db / 10)             */
+    int L, M;
+    /* iMCRA (beta above is its bias factor, 1.47) */
+    double inv_b_min; /* 1 / b_min                                                   */
+    double gamma0, gamma1, zeta0;
+    int V, U; /* 1 <= U <= 32                                                        */
+    double eps; /* run(stft, eps): 1e-7 in the reference                             */
+} setk_ns_opts;
+
+/* suppressor.run(stft) (apply_ns.py:41, :48) for one stored spectrogram spec [T][F] complex64,
+ * host or device: gain [T][F] float64 (SETK_NS_OUT_GAIN) and / or out [T][F] complex64 = gain x
+ * spec (SETK_NS_OUT_SPEC, apply_ns.py:42's operand), host or device; an output whose flag is not
+ * set may be NULL.  status (one int, host or device, may be NULL): SETK_NUM_NONFINITE for NaN /
+ * inf in the input or a non-finite gain.  iMCRA has no floor under its a-posteriori SNR
+ * (:272): a cell of digital silence makes the reference's integral diverge and every later frame
+ * NaN; here E1 alone sees that SNR floored at eps, as MCRA.run floors it (:84).
+ * SETK_ERR_UNSUPPORTED: F > 1025, a window longer than SETK_NS_MAX_TAPS or than F (np.convolve's
+ * "same" then changes its length), U > 32. */
+int setk_ns_gain(setk_handle_t h, const setk_ns_opts* opts, const float* spec, int num_frames,
+                 int num_bins, double* gain, float* out, int* status, void* stream);
+
+/* The loop body of run() (apply_ns.py:37-49) for a batch of single-channel utterances: one STFT
+ * launch (n_fft = 512 plan), one launch of the recursion, and for waveforms one inverse-STFT
+ * launch (inverse_stft(gain * stft) without norm, :42).
+ *   audio[u]   device float32 [num_samples[u]]; with SETK_FLAG_IN_PCM16 device int16
+ *              [num_samples[u]] as the wave file stores it, scaled by 2^-15 on the device
+ *   wave[u]    SETK_NS_OUT_SPEC: device float32 [L_u], L_u = setk_istft_num_samples(T_u, -1), or
+ *              int16 with SETK_FLAG_OUT_PCM16 (libsndfile's float -> PCM_16); may be NULL otherwise
+ *   gain[u]    SETK_NS_OUT_GAIN: device float64 [T_u][257]; may be NULL otherwise
+ *   status[u]  as setk_ns_gain, host or device, or NULL
+ * flags: SETK_FLAG_IN_PCM16 | SETK_FLAG_OUT_PCM16; what comes out is opts->flags.  The pointer
+ * tables and num_samples are HOST arrays of n_utts entries; scratch comes from the handle's arena;
+ * the call returns when the work has run.  Every utterance has the bits of setk_stft ->
+ * setk_ns_gain -> setk_istft on its own.  With setk_set_profiling the stage times of
+ * setk_last_stage_ms are out[0] conversion + STFT, out[1] the recursion, out[2] inverse STFT,
+ * out[3] rounding to 16 bits. */
+int setk_ns_batch(setk_handle_t h, const setk_ns_opts* opts, int n_utts, const void* const* audio,
+                  const int* num_samples, void* const* wave, double* const* gain, int* status,
+                  int flags, void* stream);
+
+/* The exponential integral E1(x) = int_x^inf exp(-t) / t dt of libs/ns.py:65-66 on its own:
+ * y[i] = E1(x[i]) for x > 0 (float64, host or device), relative error below 1e-13; 0 where it
+ * underflows (x > 745). */
+int setk_expint_e1(setk_handle_t h, const double* x, double* y, int n, void* stream);
+
 /* ---- fused hot path ------------------------------------------------------
  * The compute body of apply_adaptive_beamformer.py:130-178 for a batch of
  * utterances that share the channel count, in four kernel stages:

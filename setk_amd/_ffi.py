@@ -132,6 +132,46 @@ def spatial_width(opts, F):
     return (2 if opts.kind == SPATIAL_KINDS["cos_sin_ipd"] else 1) * opts.n_pairs * F
 
 
+NS_KINDS = {"mcra": 0, "imcra": 1}  # SETK_NS_*
+NS_OUT_GAIN = 1
+NS_OUT_SPEC = 2
+NS_MAX_TAPS = 63
+
+
+class NsOpts(ctypes.Structure):
+    _fields_ = [("kind", c_int), ("flags", c_int), ("alpha", ctypes.c_double), ("alpha_s", ctypes.c_double),
+                ("alpha_d", ctypes.c_double), ("gmin", ctypes.c_double), ("xi_min", ctypes.c_double),
+                ("n_mcra", c_int), ("n_local", c_int), ("n_global", c_int),
+                ("w_mcra", POINTER(ctypes.c_double)), ("w_local", POINTER(ctypes.c_double)),
+                ("w_global", POINTER(ctypes.c_double)),
+                ("delta", ctypes.c_double), ("beta", ctypes.c_double), ("alpha_p", ctypes.c_double),
+                ("q_max", ctypes.c_double), ("zeta_min", ctypes.c_double), ("zeta_max", ctypes.c_double),
+                ("zeta_p_min", ctypes.c_double), ("zeta_p_max", ctypes.c_double), ("L", c_int), ("M", c_int),
+                ("inv_b_min", ctypes.c_double), ("gamma0", ctypes.c_double), ("gamma1", ctypes.c_double),
+                ("zeta0", ctypes.c_double), ("V", c_int), ("U", c_int), ("eps", ctypes.c_double)]
+
+
+def ns_opts(kind, eps=1e-7, gain=True, spec=False, w_mcra=None, w_local=None, w_global=None, **values):
+    """setk_ns_opts for a kind name ("mcra" / "imcra"): the windows as float64 tap arrays, every
+    other field of the structure by its name.  The returned structure keeps its taps alive."""
+    o = NsOpts(kind=NS_KINDS[kind], flags=(NS_OUT_GAIN if gain else 0) | (NS_OUT_SPEC if spec else 0),
+               eps=float(eps))
+    for name, w in (("mcra", w_mcra), ("local", w_local), ("global", w_global)):
+        if w is None:
+            continue
+        w = [float(v) for v in w]
+        keep = (ctypes.c_double * len(w))(*w)
+        setattr(o, "_w_" + name, keep)
+        setattr(o, "w_" + name, ctypes.cast(keep, POINTER(ctypes.c_double)))
+        setattr(o, "n_" + name, len(w))
+    known = {f[0] for f in NsOpts._fields_}
+    for name, v in values.items():
+        if name not in known:
+            raise TypeError(f"setk_ns_opts has no field {name}")
+        setattr(o, name, v)
+    return o
+
+
 class SetkError(RuntimeError):
     pass
 
@@ -198,7 +238,7 @@ def exported_symbols():
         "setk_pcm16_to_float", "setk_pcm16_to_float_batch", "setk_pcm16_channel_stride", "setk_pcm16_deinterleave_batch", "setk_kaldi_cm_decode_batch", "setk_float_to_pcm16", "setk_ban", "setk_rank1", "setk_beamform", "setk_cgmm_masks", "setk_cgmm_masks_k", "setk_cgmm_masks_k_status",
         "setk_cgmm_masks_batch", "setk_cgmm_estimate_batch", "setk_cacgmm_masks", "setk_cacgmm_estimate_batch", "setk_enhance_batch", "setk_enhance_batch_taps",
         "setk_apply_weights_batch",
-        "setk_directional_feats", "setk_wpe", "setk_wpe_step", "setk_wpe_batch", "setk_wpe_batch_fnt", "setk_wpe_batch_var", "setk_auxiva", "setk_auxiva_batch", "setk_ssl_scores", "setk_ssl_batch", "setk_spatial_feats", "setk_spatial_batch", "setk_set_profiling",
+        "setk_directional_feats", "setk_wpe", "setk_wpe_step", "setk_wpe_batch", "setk_wpe_batch_fnt", "setk_wpe_batch_var", "setk_auxiva", "setk_auxiva_batch", "setk_ssl_scores", "setk_ssl_batch", "setk_spatial_feats", "setk_spatial_batch", "setk_ns_gain", "setk_ns_batch", "setk_expint_e1", "setk_set_profiling",
         "setk_last_stage_ms",
         "setk_comm_unique_id", "setk_comm_create", "setk_comm_allreduce_f64", "setk_comm_barrier",
         "setk_comm_destroy", "setk_comm_last_error", "setk_host_read_payloads"
@@ -317,6 +357,10 @@ def load_library():
     lib.setk_spatial_feats.argtypes = [H, POINTER(SpatialOpts), fp, c_int, c_int, c_int, fp, c_void_p]
     lib.setk_spatial_batch.argtypes = [H, POINTER(SpatialOpts), c_int, c_int, POINTER(c_void_p), POINTER(c_int),
                                        c_int, POINTER(c_void_p), c_void_p]
+    lib.setk_ns_gain.argtypes = [H, POINTER(NsOpts), fp, c_int, c_int, fp, fp, fp, c_void_p]
+    lib.setk_ns_batch.argtypes = [H, POINTER(NsOpts), c_int, POINTER(c_void_p), POINTER(c_int), POINTER(c_void_p),
+                                  POINTER(c_void_p), fp, c_int, c_void_p]
+    lib.setk_expint_e1.argtypes = [H, fp, fp, c_int, c_void_p]
     lib.setk_directional_feats.argtypes = [H, fp, fp, POINTER(c_int), c_int, c_int, c_int, c_int,
                                            fp, c_void_p]
     lib.setk_apply_weights_batch.argtypes = [
@@ -896,6 +940,34 @@ class Context:
         self.check(
             self._lib.setk_spatial_batch(self._h, ctypes.byref(opts), n, int(C), SP, NF, int(F), OP,
                                          current_stream_ptr() if stream is None else stream))
+
+    def ns_gain(self, opts, spec, T, F, gain=None, out=None, status=None, stream=None):
+        """MCRA.run / iMCRA.run of libs/ns.py on one spectrogram spec [T][F] complex64: gain [T][F]
+        float64 and / or out [T][F] complex64 = gain x spec as opts.flags select (numpy arrays,
+        device tensors or device addresses); status int32[1] or None."""
+        self.check(
+            self._lib.setk_ns_gain(self._h, ctypes.byref(opts), _ptr(spec), int(T), int(F), _ptr(gain), _ptr(out),
+                                   _ptr(status), current_stream_ptr() if stream is None else stream))
+
+    def ns_batch(self, opts, audio_ptrs, num_samples, wave_ptrs=None, gain_ptrs=None, status=None, flags=0,
+                 stream=None):
+        """Single-channel audio in (device addresses; int16 with FLAG_IN_PCM16), waveforms (float32,
+        or int16 with FLAG_OUT_PCM16) and / or gains float64 [T_u][257] out as opts.flags select;
+        status int32[n] (numpy or device address) or None."""
+        n = len(audio_ptrs)
+        A = (c_void_p * n)(*audio_ptrs)
+        NS = (c_int * n)(*[int(v) for v in num_samples])
+        W = (c_void_p * n)(*wave_ptrs) if wave_ptrs is not None else None
+        G = (c_void_p * n)(*gain_ptrs) if gain_ptrs is not None else None
+        self.check(
+            self._lib.setk_ns_batch(self._h, ctypes.byref(opts), n, A, NS, W, G, _ptr(status), int(flags),
+                                    current_stream_ptr() if stream is None else stream))
+
+    def expint_e1(self, x, y, stream=None):
+        """y = E1(x), float64 (numpy arrays or device tensors of the same size)."""
+        n = x.size if isinstance(x, np.ndarray) else x.numel()
+        self.check(self._lib.setk_expint_e1(self._h, _ptr(x), _ptr(y), int(n),
+                                            current_stream_ptr() if stream is None else stream))
 
     def set_profiling(self, on):
         self.check(self._lib.setk_set_profiling(self._h, 1 if on else 0))

@@ -346,4 +346,34 @@ hipError_t launch_spatial_srp_pairs(const SslUtt* d_obs, const SpatialUtt* d_utt
 hipError_t launch_spatial_srp_combine(const SpatialUtt* d_utts, const float* d_weight, int n_utts, int max_frames,
                                       int D, int P, hipStream_t s);
 
+// OM-LSA noise suppression with MCRA / iMCRA noise tracking (ns.hip): one workgroup per
+// utterance, the bins over the lanes, a loop over the frames; float64 throughout.
+constexpr int kNsMcra = 0, kNsImcra = 1;  // = SETK_NS_*
+constexpr int kNsMaxBins = 1025;          // n_fft <= 2048
+constexpr int kNsMaxHalf = 31;            // a smoothing window has at most 2 x 31 + 1 taps
+constexpr int kNsMaxRing = 32;            // iMCRA: U
+struct NsParams {
+    int kind, F;
+    int half_m, half_l, half_g;  // half widths of w_mcra / w_local / w_global
+    int L, mean_bins;            // MCRA: the reset period, min(M / 2 + 1, F)
+    int V, U;                    // iMCRA
+    int pad_;
+    double alpha, alpha_s, alpha_d, alpha_p, beta, delta, gmin, xi_min, q_max;
+    double zeta_min, zeta_max, zeta_p_min, zeta_p_max;  // MCRA, linear
+    double inv_b_min, gamma0, gamma1, zeta0;            // iMCRA
+    double eps;
+    double taps[3][2 * kNsMaxHalf + 1];  // w_mcra | w_local | w_global, as np.convolve takes them
+};
+struct NsUtt {
+    const float* spec;  // [T][F] complex64
+    double* gain;       // [T][F] or null
+    float* out;         // gain x spec, [T][F] complex64, or null
+    int* status;        // one word
+    int T;
+    int pad_;
+};
+bool ns_supported(int F);
+hipError_t launch_ns(const NsUtt* d_utts, const NsParams* d_params, int kind, int n_utts, int F, hipStream_t s);
+hipError_t launch_expint_e1(const double* x, double* y, int n, hipStream_t s);
+
 }  // namespace setk

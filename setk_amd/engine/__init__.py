@@ -14,3 +14,4 @@ from .auxiva import BatchSeparator  # noqa: F401
 from .ssl import BatchLocalizer  # noqa: F401
 from .directional import BatchDirectionalFeatures  # noqa: F401
 from .spatial import BatchSpatialFeatures  # noqa: F401
+from .ns import BatchNoiseSuppressor  # noqa: F401
