@@ -33,6 +33,7 @@ from setk_amd.libs.data_handler import (NumpyReader, ScriptReader, SpectrogramRe
                                         WaveReader, WaveWriter)
 from setk_amd.libs.opts import StftParser, strtobool
 from setk_amd.libs.utils import get_logger, inverse_stft, nextpow2
+from setk_amd.sptk._common import complete_wav as _complete_wav, deal, finish, run_batches, stft_kwargs
 
 logger = get_logger(__name__)
 beamformers = ["mvdr", "mpdr", "mpdr-whiten", "gevd", "pmwf-0", "pmwf-1"]
@@ -139,25 +140,6 @@ def do_online_beamform(beamformer, speech_mask, interf_mask, stft_mat, args):
     return np.hstack(out)
 
 
-def _complete_wav(path):
-    """True if `path` is a WAV file whose size is what its RIFF / data chunk headers say (the
-    writer renames finished files into place; this also rejects files truncated by other
-    means, e.g. a full disk under an older version)."""
-    try:
-        size = os.path.getsize(path)
-        if size <= 44:
-            return False
-        with open(path, "rb") as f:
-            head = f.read(44)
-    except OSError:
-        return False
-    if len(head) < 44 or head[:4] != b"RIFF" or head[8:12] != b"WAVE" or head[36:40] != b"data":
-        return False
-    riff = int.from_bytes(head[4:8], "little")
-    data = int.from_bytes(head[40:44], "little")
-    return riff + 8 == size and data + 44 == size
-
-
 def _arm_fault_injection(shard, writer):
     """Test hook of the re-queue path (tests/test_host_asan.py): SETK_FAULT_INJECT=
     "<rank>:<n>[:<attempt>]" makes that rank die WITHOUT any clean-up -- as a killed process
@@ -185,35 +167,9 @@ def _arm_fault_injection(shard, writer):
     writer.record = wrap(writer.record)   # every finished file passes through record()
 
 
-def _deal(args, shard, reader):
-    """This rank's utterances.  Default: the deal is computed on the FULL table (every rank keeps
-    the utterances it had) and --skip-existing then drops what is already there.  --requeue
-    (a re-launch after a failure): the missing utterances are found first -- by every rank, from
-    the same directory listing: nobody writes before the barrier below -- and only they are dealt,
-    so the leftovers of a rank that died are shared by all ranks instead of waiting for it."""
-    if getattr(args, "skip_existing", False) and getattr(args, "requeue", False) and shard.world > 1:
-        left = _drop_existing(args, list(reader.index_keys))
-        shard.barrier()
-        return shard.assign_by_duration(reader, keys=left)
-    return _drop_existing(args, shard.assign_by_duration(reader))
-
-
-def _drop_existing(args, keys):
-    """--skip-existing: a re-run after an interruption (or a re-queued shard of a failed
-    rank) only does what is missing.  The sharding above is computed on the full table, so
-    every rank keeps the utterances it had."""
-    if not getattr(args, "skip_existing", False):
-        return keys
-    left = []
-    for k in keys:
-        path = os.path.join(args.dst_dir, f"{k}.wav")
-        done = _complete_wav(path)
-        if not done:
-            left.append(k)
-    if len(left) != len(keys):
-        logger.info(f"--skip-existing: {len(keys) - len(left)} of {len(keys)} utterances already "
-                    f"in {args.dst_dir}")
-    return left
+def _wav_done(args):
+    """done(key) of the shared deal: --skip-existing leaves out a key whose {dst_dir}/{key}.wav is complete."""
+    return lambda key: _complete_wav(os.path.join(args.dst_dir, f"{key}.wav"))
 
 
 def run_online(args, shard):
@@ -231,7 +187,7 @@ def run_online(args, shard):
     beamformer = cls(num_bins, args.channels, args.alpha)
     logger.info(f"Using online {args.beamformer} beamformer, chunk size = {args.chunk_size:d}")
     num_done = 0
-    keys = _deal(args, shard, reader)
+    keys = deal(args, shard, reader, _wav_done(args))
     with WaveWriter(args.dst_dir, sr=args.sr) as writer:
         for key in keys:
             if key not in tgt:
@@ -317,9 +273,7 @@ def run_offline(args, shard):
         # single-process run never imports torch (0.9 s of a 2 s run on 192 utterances)
         # (more than 8 channels run the unfused engine through torch tensors)
         _ffi.set_torch_free(wav_reader.first_channels_at_most(8))
-    engine = BatchEnhancer(beamformer=args.beamformer, frame_len=args.frame_len,
-                           frame_hop=args.frame_hop, center=bool(args.center),
-                           round_power_of_two=bool(args.round_power_of_two), window=args.window,
+    engine = BatchEnhancer(beamformer=args.beamformer, **stft_kwargs(args),
                            ban=bool(args.ban), pmwf_ref=args.pmwf_ref,
                            rank1_appro=args.rank1_appro, post_mask=bool(args.mask),
                            vad_proportion=args.vad_proportion, pcm16=True, device=device,
@@ -331,7 +285,7 @@ def run_offline(args, shard):
     if placement.get("bound"):
         logger.info(f"rank {shard.rank}: bound to NUMA node {placement['node']} "
                     f"({placement['cpus']} CPUs, GPU {placement.get('pci_bus_id')})")
-    keys = _deal(args, shard, wav_reader)
+    keys = deal(args, shard, wav_reader, _wav_done(args))
     mark("numa_bound_keys_dealt")
     summary = dict(mode="batch", utts=0, rank=shard.rank, world=shard.world,
                    assigned_samples=shard.assigned_weight, numa=placement, marks=marks)
@@ -422,12 +376,9 @@ def _run_pipeline(args, engine, writer, wav_reader, tgt, itf, keys):
 
 def _run_batches(args, engine, writer, wav_reader, tgt, itf, keys):
     """One batch at a time (n_fft != 512, VAD filtering, --pipeline false)."""
-    num_done = 0
 
     def flush(pending):
         done = 0
-        if not pending:
-            return done
         results = engine.enhance([(s, m, i) for (_, s, m, i) in pending])
         for (key, _, _, _), (pcm, status) in zip(pending, results):
             if status != 0:
@@ -438,29 +389,26 @@ def _run_batches(args, engine, writer, wav_reader, tgt, itf, keys):
             done += 1
         return done
 
-    pending = []
-    for key in keys:
-        if key not in tgt:
-            continue
-        pcm = wav_reader.read_pcm16(key) if args.device_ingest else None
-        if pcm is not None:
-            # 16-bit PCM file: upload the frames as stored, convert on the device
-            ch0 = pcm[:, 0].astype(np.float32) / np.float32(32768.0)
-            samps = Pcm16Frames(pcm)
-        else:
-            samps = wav_reader.read(key)
-            if samps.ndim == 1:
-                samps = samps[None]
-            ch0 = samps[0]
-        power = np.linalg.norm(ch0, 2)**2 / ch0.size
-        logger.info(f"Processing utterance {key}, " +
-                    f"signal power {10 * np.log10(power + 1e-5):.2f}...")
-        pending.append((key, samps, tgt[key], None if itf is None else itf[key]))
-        if len(pending) >= args.batch_utts:
-            num_done += flush(pending)
-            pending = []
-    num_done += flush(pending)
-    return num_done
+    def utterances():
+        for key in keys:
+            if key not in tgt:
+                continue
+            pcm = wav_reader.read_pcm16(key) if args.device_ingest else None
+            if pcm is not None:
+                # 16-bit PCM file: upload the frames as stored, convert on the device
+                ch0 = pcm[:, 0].astype(np.float32) / np.float32(32768.0)
+                samps = Pcm16Frames(pcm)
+            else:
+                samps = wav_reader.read(key)
+                if samps.ndim == 1:
+                    samps = samps[None]
+                ch0 = samps[0]
+            power = np.linalg.norm(ch0, 2)**2 / ch0.size
+            logger.info(f"Processing utterance {key}, " +
+                        f"signal power {10 * np.log10(power + 1e-5):.2f}...")
+            yield key, samps, tgt[key], None if itf is None else itf[key]
+
+    return run_batches(utterances(), args.batch_utts, flush)
 
 
 def run(args):
@@ -473,11 +421,7 @@ def run(args):
                 raise RuntimeError(f"Seems chunk size({args.chunk_size:.2f}) " +
                                    "too small for online beamformer")
             num_done, total = run_online(args, shard)
-        shard.barrier()
-        if shard.world > 1:
-            num_done = int(round(shard.sum_counts([num_done])[0]))
-        if shard.rank == 0:
-            logger.info(f"Processed {num_done:d} utterances out of {total:d}")
+        finish(shard, num_done, f"Processed %d utterances out of {total:d}")
     finally:
         shard.close()
 

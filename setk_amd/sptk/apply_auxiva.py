@@ -16,16 +16,19 @@ or all-zero channel) is logged and skipped like apply_adaptive_beamformer.py:170
 the reference's run ends there with LinAlgError.
 """
 import argparse
+from contextlib import closing
 
 import numpy as np
 
-from .. import _ffi
-from .._ffi import SetkUnsupported
+from setk_amd import _ffi
+from setk_amd._ffi import SetkUnsupported
 from setk_amd.dist import Shard
-from setk_amd.engine import BatchSeparator, Pcm16Frames, channels_and_size
+from setk_amd.engine import BatchSeparator
 from setk_amd.libs.data_handler import WaveReader, WaveWriter
 from setk_amd.libs.opts import StftParser
 from setk_amd.libs.utils import get_logger
+from setk_amd.sptk._common import (finish, group_by_channels, read_samples, run_batches,
+                                   set_torch_free, stft_kwargs)
 
 logger = get_logger(__name__)
 
@@ -62,63 +65,45 @@ def auxiva(X, epochs=20):
 
 
 def run(args):
-    shard = Shard()
-    device = shard.device if shard.world > 1 else None
-    n_fft = 2**int(np.ceil(np.log2(args.frame_len))) if args.round_power_of_two else args.frame_len
-    reader = WaveReader(args.wav_scp)  # 16 kHz tables like the reference (SpectrogramReader)
-    if n_fft == 512 and shard.torch_free_ok:
-        # the engine brings its own buffers and stream
-        _ffi.set_torch_free(True)
-    engine = BatchSeparator(num_epochs=args.epochs, frame_len=args.frame_len,
-                            frame_hop=args.frame_hop, center=bool(args.center),
-                            round_power_of_two=bool(args.round_power_of_two), window=args.window,
-                            device=device, pcm16=True)
-    num_done = 0
-    with WaveWriter(args.dst_dir, sr=args.sr) as writer:
+    with closing(Shard()) as shard:
+        reader = WaveReader(args.wav_scp)  # 16 kHz tables like the reference (SpectrogramReader)
+        set_torch_free(args, shard)
+        engine = BatchSeparator(num_epochs=args.epochs, device=shard.device if shard.world > 1 else None,
+                                pcm16=True, **stft_kwargs(args))
+        with closing(engine), WaveWriter(args.dst_dir, sr=args.sr) as writer:
 
-        def flush(pending):
-            """--batch-utts utterances (grouped by channel count) per engine call."""
-            done = 0
-            groups = {}
-            for key, samps in pending:
-                groups.setdefault(channels_and_size(samps)[0], []).append((key, samps))
-            for nch, items in groups.items():
-                if nch > MAX_CHANNELS:
-                    for key, _ in items:
-                        logger.warning(f"{key}: skipped, AuxIVA on the device needs 1 <= channels "
-                                       f"<= {MAX_CHANNELS} (got {nch} channels)")
-                    continue
-                try:
-                    outs = engine.run([s for _, s in items])
-                except SetkUnsupported as e:
-                    for key, _ in items:
-                        logger.warning(f"{key}: skipped, {e}")
-                    continue
-                for (key, _), srcs, st in zip(items, outs, engine.status):
-                    if srcs is None:
-                        what = "LinAlgError (Singular matrix)" if st == _ffi.NUM_SINGULAR else "non-finite values"
-                        logger.warning(f"{key}: Failed cause {what} in auxiva")
+            def flush(pending):
+                """--batch-utts utterances (grouped by channel count) per engine call."""
+                done = 0
+                for nch, items in group_by_channels(pending).items():
+                    if nch > MAX_CHANNELS:
+                        for key, _ in items:
+                            logger.warning(f"{key}: skipped, AuxIVA on the device needs 1 <= channels "
+                                           f"<= {MAX_CHANNELS} (got {nch} channels)")
                         continue
-                    for idx in range(srcs.shape[0]):
-                        writer.write_pcm16(f"{key}.src{idx + 1}", srcs[idx])
-                    done += 1
-            return done
+                    try:
+                        outs = engine.run([s for _, s in items])
+                    except SetkUnsupported as e:
+                        for key, _ in items:
+                            logger.warning(f"{key}: skipped, {e}")
+                        continue
+                    for (key, _), srcs, st in zip(items, outs, engine.status):
+                        if srcs is None:
+                            what = "LinAlgError (Singular matrix)" if st == _ffi.NUM_SINGULAR else "non-finite values"
+                            logger.warning(f"{key}: Failed cause {what} in auxiva")
+                            continue
+                        for idx in range(srcs.shape[0]):
+                            writer.write_pcm16(f"{key}.src{idx + 1}", srcs[idx])
+                        done += 1
+                return done
 
-        pending = []
-        for key in shard.assign_by_duration(reader):
-            logger.info(f"Processing utterance {key}...")
-            pcm = reader.read_pcm16(key)
-            pending.append((key, Pcm16Frames(pcm) if pcm is not None else reader.read(key)))
-            if len(pending) >= max(1, args.batch_utts):
-                num_done += flush(pending)
-                pending = []
-        num_done += flush(pending)
-    shard.barrier()
-    if shard.world > 1:
-        num_done = int(round(shard.sum_counts([num_done])[0]))
-    if shard.rank == 0:
-        logger.info(f"Processed {num_done:d} utterances over {len(reader):d}")
-    shard.close()
+            def utterances():
+                for key in shard.assign_by_duration(reader):
+                    logger.info(f"Processing utterance {key}...")
+                    yield key, read_samples(reader, key)
+
+            num_done = run_batches(utterances(), args.batch_utts, flush)
+        finish(shard, num_done, f"Processed %d utterances over {len(reader):d}")
 
 
 def build_parser():

@@ -15,17 +15,18 @@ stand-alone operators, as the reference does (:20-31).
 """
 import argparse
 import math
+from contextlib import closing
 
 import numpy as np
 
-from setk_amd import _ffi
 from setk_amd.dist import Shard
-from setk_amd.engine import FixedBatchBeamformer, Pcm16Frames
+from setk_amd.engine import FixedBatchBeamformer, channels_and_size
 from setk_amd.libs.beamformer import (CircularDSBeamformer, CircularSDBeamformer,
                                       LinearDSBeamformer, LinearSDBeamformer)
 from setk_amd.libs.data_handler import ScpReader, SpectrogramReader, WaveReader, WaveWriter
 from setk_amd.libs.opts import StftParser, str2tuple, strtobool
-from setk_amd.libs.utils import check_doa, get_logger, inverse_stft, nextpow2
+from setk_amd.libs.utils import check_doa, get_logger, inverse_stft
+from setk_amd.sptk._common import finish, n_fft, read_samples, run_batches, set_torch_free, stft_kwargs
 
 logger = get_logger(__name__)
 beamformers = ["ds", "sd"]
@@ -103,14 +104,11 @@ def run_online(args, beamformer, utt2doa, shard):
 
 
 def run_offline(args, beamformer, utt2doa, shard):
-    n_fft = nextpow2(args.frame_len) if args.round_power_of_two else args.frame_len
-    num_bins = n_fft // 2 + 1
+    num_bins = n_fft(args) // 2 + 1
     wav_reader = WaveReader(args.wav_scp, sr=args.sr)
     device = shard.device if shard.world > 1 else None
-    if n_fft == 512 and shard.torch_free_ok:
-        # the batch engine brings its own buffers and stream (more than 8 channels: torch)
-        _ffi.set_torch_free(wav_reader.first_channels_at_most(8))
-    done = 0
+    # the batch engine brings its own buffers and stream (more than 8 channels: torch)
+    set_torch_free(args, shard, wav_reader.first_channels_at_most(8))
     # ONE engine for the run (pinned slabs, device twin and stream are allocated once, not per
     # batch), the DS / SD weights computed once per DoA (SD: an N x N solve per bin) and the
     # engine's table replaced only when a batch brings a DoA not seen before
@@ -119,18 +117,14 @@ def run_offline(args, beamformer, utt2doa, shard):
     with WaveWriter(args.dst_dir, sr=args.sr) as writer:
 
         def flush(pending):
-            if not pending:
-                return 0
             for (_, _, d) in pending:
                 if d not in wcache:
                     wcache[d] = beamformer.weight(d, num_bins, c=args.speed, sr=args.sr)
                     order.append(d)
             if state["engine"] is None:
                 state["engine"] = FixedBatchBeamformer(
-                    np.stack([wcache[d] for d in order]), frame_len=args.frame_len,
-                    frame_hop=args.frame_hop, center=bool(args.center),
-                    round_power_of_two=bool(args.round_power_of_two), window=args.window, pcm16=True,
-                    device=device, renorm=bool(args.normalize))
+                    np.stack([wcache[d] for d in order]), pcm16=True, device=device,
+                    renorm=bool(args.normalize), **stft_kwargs(args))
             elif state["rows"] != len(order):
                 state["engine"].set_weights(np.stack([wcache[d] for d in order]))
             state["rows"] = len(order)
@@ -139,28 +133,24 @@ def run_offline(args, beamformer, utt2doa, shard):
                 writer.write_pcm16(key, pcm)
             return len(pending)
 
-        pending = []
-        for key in shard.assign_by_duration(wav_reader):
-            doa = utt2doa(key)
-            if doa is None:
-                logger.info(f"Missing doa for utterance {key}")
-                continue
-            if not check_doa(args.geometry, doa, False):
-                logger.info(f"Invalid doa {doa:.2f} for utterance {key}")
-                continue
-            pcm = wav_reader.read_pcm16(key)
-            samps = Pcm16Frames(pcm) if pcm is not None else wav_reader.read(key)
-            nch = samps.num_channels if isinstance(samps, Pcm16Frames) else \
-                (1 if samps.ndim == 1 else samps.shape[0])
-            if nch != beamformer.num_mics:
-                raise ValueError("Shape of obs do not match with number" +
-                                 f"of microphones, {beamformer.num_mics} vs {nch}")
-            pending.append((key, samps, doa))
-            if len(pending) >= args.batch_utts:
-                done += flush(pending)
-                pending = []
+        def utterances():
+            for key in shard.assign_by_duration(wav_reader):
+                doa = utt2doa(key)
+                if doa is None:
+                    logger.info(f"Missing doa for utterance {key}")
+                    continue
+                if not check_doa(args.geometry, doa, False):
+                    logger.info(f"Invalid doa {doa:.2f} for utterance {key}")
+                    continue
+                samps = read_samples(wav_reader, key)
+                nch = channels_and_size(samps)[0]
+                if nch != beamformer.num_mics:
+                    raise ValueError("Shape of obs do not match with number" +
+                                     f"of microphones, {beamformer.num_mics} vs {nch}")
+                yield key, samps, doa
+
         try:
-            done += flush(pending)
+            done = run_batches(utterances(), args.batch_utts, flush)
         finally:
             if state["engine"] is not None:
                 state["engine"].close()
@@ -171,16 +161,12 @@ def run(args):
     beamformer = make_beamformer(args)
     online = args.chunk_len > 0
     utt2doa = parse_doa(args, online)
-    shard = Shard()
-    if online:
-        done, total = run_online(args, beamformer, utt2doa, shard)
-    else:
-        done, total = run_offline(args, beamformer, utt2doa, shard)
-    done = int(shard.sum_counts([done])[0])
-    if shard.rank == 0:
-        logger.info(f"Processed {done} utterances over {total}")
-    shard.barrier()
-    shard.close()
+    with closing(Shard()) as shard:
+        if online:
+            done, total = run_online(args, beamformer, utt2doa, shard)
+        else:
+            done, total = run_offline(args, beamformer, utt2doa, shard)
+        finish(shard, done, f"Processed %d utterances over {total}")
 
 
 def build_parser(description="Command to apply classic beamformer (linear & circular array).",

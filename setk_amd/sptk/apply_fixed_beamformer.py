@@ -12,15 +12,16 @@ weight through the beam table and fails on it (``if beamformer:`` is true for
 an object, apply_fixed_beamformer.py:41-43); here that case simply works.
 """
 import argparse
+from contextlib import closing
 
 import numpy as np
 
-from setk_amd import _ffi
 from setk_amd.dist import Shard
-from setk_amd.engine import FixedBatchBeamformer, Pcm16Frames
+from setk_amd.engine import FixedBatchBeamformer
 from setk_amd.libs.data_handler import ScpReader, WaveReader, WaveWriter
 from setk_amd.libs.opts import StftParser
 from setk_amd.libs.utils import get_logger
+from setk_amd.sptk._common import finish, read_samples, run_batches, set_torch_free, stft_kwargs
 
 logger = get_logger(__name__)
 
@@ -36,45 +37,28 @@ def run(args):
         beam_index = ScpReader(args.beam, value_processor=int)
     else:
         raise RuntimeError(f"Expect weights in shape F x M or B x F x M, got {weights.shape}")
-    shard = Shard()
-    device = shard.device if shard.world > 1 else None
-    n_fft = 2**int(np.ceil(np.log2(args.frame_len))) if args.round_power_of_two else args.frame_len
-    if n_fft == 512 and shard.torch_free_ok:
+    with closing(Shard()) as shard:
         # the batch engine brings its own buffers and stream (more than 8 channels: torch)
-        _ffi.set_torch_free(weights.shape[-1] <= 8)
-    engine = FixedBatchBeamformer(weights, frame_len=args.frame_len, frame_hop=args.frame_hop,
-                                  center=bool(args.center),
-                                  round_power_of_two=bool(args.round_power_of_two),
-                                  window=args.window, pcm16=True, device=device)
-    wav_reader = WaveReader(args.wav_scp)
-    keys = shard.assign_by_duration(wav_reader)
-    num_done = 0
-    with WaveWriter(args.dst_dir) as writer:
+        set_torch_free(args, shard, weights.shape[-1] <= 8)
+        engine = FixedBatchBeamformer(weights, pcm16=True, device=shard.device if shard.world > 1 else None,
+                                      **stft_kwargs(args))
+        wav_reader = WaveReader(args.wav_scp)
+        keys = shard.assign_by_duration(wav_reader)
+        with closing(engine), WaveWriter(args.dst_dir) as writer:
 
-        def flush(pending):
-            if not pending:
-                return 0
-            outs = engine.run([(s, b) for (_, s, b) in pending])
-            for (key, _, _), pcm in zip(pending, outs):
-                writer.write_pcm16(key, pcm)
-            return len(pending)
+            def flush(pending):
+                outs = engine.run([(s, b) for (_, s, b) in pending])
+                for (key, _, _), pcm in zip(pending, outs):
+                    writer.write_pcm16(key, pcm)
+                return len(pending)
 
-        pending = []
-        for key in keys:
-            logger.info(f"Processing utterance {key}...")
-            pcm = wav_reader.read_pcm16(key)
-            samps = Pcm16Frames(pcm) if pcm is not None else wav_reader.read(key)
-            beam = 0 if beam_index is None else beam_index[key]
-            pending.append((key, samps, beam))
-            if len(pending) >= args.batch_utts:
-                num_done += flush(pending)
-                pending = []
-        num_done += flush(pending)
-    total = int(shard.sum_counts([num_done])[0])
-    if shard.rank == 0:
-        logger.info(f"Processed {total:d} utterances")
-    shard.barrier()
-    shard.close()
+            def utterances():
+                for key in keys:
+                    logger.info(f"Processing utterance {key}...")
+                    yield key, read_samples(wav_reader, key), 0 if beam_index is None else beam_index[key]
+
+            num_done = run_batches(utterances(), args.batch_utts, flush)
+        finish(shard, num_done, "Processed %d utterances")
 
 
 def build_parser():

@@ -15,45 +15,18 @@ What differs on purpose is listed in tests/PARITY_NOTES_NS.md (digital silence s
 """
 import argparse
 import os
+from contextlib import closing
 
-import numpy as np
-
-from .. import _ffi
 from setk_amd.dist import Shard
-from setk_amd.engine import BatchNoiseSuppressor, Pcm16Frames, channels_and_size
+from setk_amd.engine import BatchNoiseSuppressor, channels_and_size
 from setk_amd.libs.data_handler import NumpyWriter, WaveReader, WaveWriter
 from setk_amd.libs.ns import iMCRA
 from setk_amd.libs.opts import StftParser, strtobool
 from setk_amd.libs.utils import get_logger
-from setk_amd.sptk.apply_adaptive_beamformer import _complete_wav
+from setk_amd.sptk._common import (complete_npy, complete_wav, deal, finish, read_samples, run_batches,
+                                   set_torch_free, stft_kwargs)
 
 logger = get_logger(__name__)
-
-
-def _done(args, key):
-    if args.output == "wave":
-        return _complete_wav(os.path.join(args.dst_dir, f"{key}.wav"))
-    try:
-        np.load(os.path.join(args.dst_dir, f"{key}.npy"), mmap_mode="r")
-        return True
-    except (OSError, ValueError):
-        return False
-
-
-def _deal(args, shard, reader):
-    """This rank's utterances; --skip-existing drops what is already there, --requeue (what
-    setk_amd.launch passes on a retry) first finds what is missing and deals only that."""
-    if not args.skip_existing:
-        return shard.assign_by_duration(reader)
-    if args.requeue and shard.world > 1:
-        left = [k for k in reader.index_keys if not _done(args, k)]
-        shard.barrier()
-        return shard.assign_by_duration(reader, keys=left)
-    keys = shard.assign_by_duration(reader)
-    left = [k for k in keys if not _done(args, k)]
-    if len(left) != len(keys):
-        logger.info(f"--skip-existing: {len(keys) - len(left)} of {len(keys)} utterances already in {args.dst_dir}")
-    return left
 
 
 def run(args):
@@ -65,59 +38,50 @@ def run(args):
             suppressor = iMCRA(**(yaml.full_load(conf) or {}))
     else:
         suppressor = iMCRA()
-    shard = Shard()
-    device = shard.device if shard.world > 1 else None
-    n_fft = 2**int(np.ceil(np.log2(args.frame_len))) if args.round_power_of_two else args.frame_len
-    reader = WaveReader(args.wav_scp)  # 16 kHz tables like the reference (SpectrogramReader)
-    if n_fft == 512 and shard.torch_free_ok:
-        _ffi.set_torch_free(True)  # the engine brings its own buffers and stream
     wave = args.output == "wave"
-    engine = BatchNoiseSuppressor(suppressor, output=args.output, frame_len=args.frame_len,
-                                  frame_hop=args.frame_hop, center=bool(args.center),
-                                  round_power_of_two=bool(args.round_power_of_two), window=args.window,
-                                  device=device, pcm16=True)
-    num_done = 0
-    with (WaveWriter(args.dst_dir, sr=args.sr) if wave else NumpyWriter(args.dst_dir)) as writer:
 
-        def flush(pending):
-            done = 0
-            ok = []
-            for key, samps in pending:
-                if channels_and_size(samps)[0] != 1:
-                    logger.warning(f"{key}: skipped, noise suppression takes single-channel audio "
-                                   f"(got {channels_and_size(samps)[0]} channels)")
-                else:
-                    ok.append((key, samps))
-            if not ok:
-                return 0
-            outs = engine.run([s for _, s in ok])
-            for (key, _), res in zip(ok, outs):
-                if res is None:
-                    logger.warning(f"{key}: skipped, non-finite values in the samples")
-                    continue
-                if wave:
-                    writer.write_pcm16(key, res)  # rounded on the device by the writer's rule
-                else:
-                    writer.write(key, res)
-                done += 1
-            return done
+    def complete(key):
+        if wave:
+            return complete_wav(os.path.join(args.dst_dir, f"{key}.wav"))
+        return complete_npy(os.path.join(args.dst_dir, f"{key}.npy"))
 
-        pending = []
-        for key in _deal(args, shard, reader):
-            logger.info(f"Processing utterance {key}...")
-            pcm = reader.read_pcm16(key)
-            pending.append((key, Pcm16Frames(pcm) if pcm is not None else reader.read(key)))
-            if len(pending) >= max(1, args.batch_utts):
-                num_done += flush(pending)
-                pending = []
-        num_done += flush(pending)
-    engine.close()
-    shard.barrier()
-    if shard.world > 1:
-        num_done = int(round(shard.sum_counts([num_done])[0]))
-    if shard.rank == 0:
-        logger.info(f"Processed {num_done:d} utterances done")
-    shard.close()
+    with closing(Shard()) as shard:
+        reader = WaveReader(args.wav_scp)  # 16 kHz tables like the reference (SpectrogramReader)
+        set_torch_free(args, shard)  # the engine brings its own buffers and stream
+        engine = BatchNoiseSuppressor(suppressor, output=args.output, pcm16=True,
+                                      device=shard.device if shard.world > 1 else None, **stft_kwargs(args))
+        with closing(engine), (WaveWriter(args.dst_dir, sr=args.sr) if wave else NumpyWriter(args.dst_dir)) as writer:
+
+            def flush(pending):
+                done = 0
+                ok = []
+                for key, samps in pending:
+                    if channels_and_size(samps)[0] != 1:
+                        logger.warning(f"{key}: skipped, noise suppression takes single-channel audio "
+                                       f"(got {channels_and_size(samps)[0]} channels)")
+                    else:
+                        ok.append((key, samps))
+                if not ok:
+                    return 0
+                outs = engine.run([s for _, s in ok])
+                for (key, _), res in zip(ok, outs):
+                    if res is None:
+                        logger.warning(f"{key}: skipped, non-finite values in the samples")
+                        continue
+                    if wave:
+                        writer.write_pcm16(key, res)  # rounded on the device by the writer's rule
+                    else:
+                        writer.write(key, res)
+                    done += 1
+                return done
+
+            def utterances():
+                for key in deal(args, shard, reader, complete):
+                    logger.info(f"Processing utterance {key}...")
+                    yield key, read_samples(reader, key)
+
+            num_done = run_batches(utterances(), args.batch_utts, flush)
+        finish(shard, num_done, "Processed %d utterances done")
 
 
 def build_parser():

@@ -12,80 +12,76 @@ renorm to max |samples| and the PCM_16 conversion run on the device, one slab co
 Utterances are dealt over the ranks of a ``torchrun`` launch by duration.
 """
 import argparse
+from contextlib import closing
 
 import numpy as np
 
-from .. import _ffi
+from setk_amd import _ffi
 from setk_amd.dist import Shard
-from setk_amd.engine import BatchWpd, Pcm16Frames
+from setk_amd.engine import BatchWpd, channels_and_size
 from setk_amd.libs.data_handler import WaveReader, WaveWriter
 from setk_amd.libs.opts import StftParser, strtobool
 from setk_amd.libs.utils import get_logger
+from setk_amd.sptk._common import finish, read_samples, stft_kwargs
 
 logger = get_logger(__name__)
 
 
 def run(args):
-    shard = Shard()
-    waves = WaveReader(args.wav_scp)
-    if shard.torch_free_ok:
-        # buffers, streams and copies come from the library (wider tables: torch tensors)
-        _ffi.set_torch_free(waves.first_channels_at_most(8))
-    engine = BatchWpd(taps=args.taps, delay=args.delay, context=args.context,
-                      wpd_iters=args.wpd_iters, cgmm_iters=args.cgmm_iters,
-                      update_alpha=bool(args.update_alpha), frame_len=args.frame_len,
-                      frame_hop=args.frame_hop, center=bool(args.center), window=args.window,
-                      round_power_of_two=bool(args.round_power_of_two), pcm16=True,
-                      device=shard.device if shard.world > 1 else None)
-    mine = shard.assign_by_duration(waves)
-    done = 0
-    with WaveWriter(args.dst_dir, sr=args.sr) as writer:
+    with closing(Shard()) as shard:
+        waves = WaveReader(args.wav_scp)
+        if shard.torch_free_ok:
+            # buffers, streams and copies come from the library (wider tables: torch tensors)
+            _ffi.set_torch_free(waves.first_channels_at_most(8))
+        engine = BatchWpd(taps=args.taps, delay=args.delay, context=args.context,
+                          wpd_iters=args.wpd_iters, cgmm_iters=args.cgmm_iters,
+                          update_alpha=bool(args.update_alpha), pcm16=True,
+                          device=shard.device if shard.world > 1 else None, **stft_kwargs(args))
+        mine = shard.assign_by_duration(waves)
+        done = 0
+        with closing(engine), WaveWriter(args.dst_dir, sr=args.sr) as writer:
 
-        def emit(group):
-            """One device batch: utterances of ONE channel count."""
-            nonlocal done
-            try:
-                results = engine.run([samps for _, samps in group])
-            except _ffi.SetkUnsupported as e:
-                # a shape beyond the device kernels (channels x taps): skipped like a numerical
-                # failure, the run goes on
-                for key, _ in group:
-                    logger.warning(f"{key}: skipped, {e}")
-                return
-            for (key, _), res in zip(group, results):
-                if res is None:
-                    logger.warning(f"{key}: Failed cause LinAlgError in wpd")
-                    continue
-                wave, mask = res
-                writer.write_pcm16(key, wave)
-                if args.dump_mask:
-                    np.save(f"{args.dst_dir}/{key}", mask.astype(np.float64))
-                done += 1
-                if done % 100 == 0:
-                    logger.info(f"Processed {done:d} utterances...")
+            def emit(group):
+                """One device batch: utterances of ONE channel count."""
+                nonlocal done
+                try:
+                    results = engine.run([samps for _, samps in group])
+                except _ffi.SetkUnsupported as e:
+                    # a shape beyond the device kernels (channels x taps): skipped like a numerical
+                    # failure, the run goes on
+                    for key, _ in group:
+                        logger.warning(f"{key}: skipped, {e}")
+                    return
+                for (key, _), res in zip(group, results):
+                    if res is None:
+                        logger.warning(f"{key}: Failed cause LinAlgError in wpd")
+                        continue
+                    wave, mask = res
+                    writer.write_pcm16(key, wave)
+                    if args.dump_mask:
+                        np.save(f"{args.dst_dir}/{key}", mask.astype(np.float64))
+                    done += 1
+                    if done % 100 == 0:
+                        logger.info(f"Processed {done:d} utterances...")
 
-        pending = {}  # channel count -> [(key, samples)]
-        for key in mine:
-            logger.info(f"Processing utt {key}...")
-            frames = waves.read_pcm16(key)
-            samps = Pcm16Frames(frames) if frames is not None else np.atleast_2d(waves.read(key))
-            group = pending.setdefault(samps.num_channels if frames is not None else samps.shape[0], [])
-            group.append((key, samps))
-            if len(group) >= args.batch_utts:
-                emit(group)
-                del group[:]
-        for group in pending.values():
-            if group:
-                emit(group)
-    if engine.rank_deficient_bins:
-        logger.warning(f"{engine.rank_deficient_bins:d} frequency bins had a rank-deficient tap correlation "
-                       "(columns at the noise level dropped; numpy.linalg.solve goes through on such input too)")
-    engine.close()
-    shard.barrier()
-    total = int(round(shard.sum_counts([done])[0])) if shard.world > 1 else done
-    if shard.rank == 0:
-        logger.info(f"Processed {total:d} utterances over {len(waves):d}")
-    shard.close()
+            # one open batch per channel count across the whole run (not the shared batch loop,
+            # which closes a batch of mixed channel counts and groups it afterwards)
+            pending = {}  # channel count -> [(key, samples)]
+            for key in mine:
+                logger.info(f"Processing utt {key}...")
+                samps = read_samples(waves, key, at_least_2d=True)
+                group = pending.setdefault(channels_and_size(samps)[0], [])
+                group.append((key, samps))
+                if len(group) >= args.batch_utts:
+                    emit(group)
+                    del group[:]
+            for group in pending.values():
+                if group:
+                    emit(group)
+        if engine.rank_deficient_bins:
+            logger.warning(f"{engine.rank_deficient_bins:d} frequency bins had a rank-deficient tap correlation "
+                           "(columns at the noise level dropped; numpy.linalg.solve goes through on such input too)")
+        finish(shard, done, f"Processed %d utterances over {len(waves):d}")
 
 
 def build_parser():

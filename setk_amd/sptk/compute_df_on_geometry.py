@@ -18,7 +18,8 @@ from setk_amd.engine import BatchSpatialFeatures
 from setk_amd.libs.data_handler import ArchiveWriter, ScpReader, WaveReader
 from setk_amd.libs.opts import StftParser
 from setk_amd.libs.utils import get_logger
-from setk_amd.sptk.compute_ipd_and_linear_srp import feed, stft_kwargs
+from setk_amd.sptk._common import stft_kwargs
+from setk_amd.sptk.compute_ipd_and_linear_srp import feed
 
 logger = get_logger(__name__)
 

@@ -16,10 +16,11 @@ import argparse
 import numpy as np
 
 from setk_amd import _ffi
-from setk_amd.engine import BatchDirectionalFeatures, Pcm16Frames
+from setk_amd.engine import BatchDirectionalFeatures
 from setk_amd.libs.data_handler import ArchiveWriter, NumpyReader, ScriptReader, WaveReader
 from setk_amd.libs.opts import StftParser
 from setk_amd.libs.utils import get_logger
+from setk_amd.sptk._common import read_samples, run_batches, stft_kwargs
 
 logger = get_logger(__name__)
 
@@ -44,18 +45,13 @@ def run(args):
     # device buffers, streams and copies come from the library unless a table is wider than the
     # fused STFT (more than 8 channels go through torch tensors)
     _ffi.set_torch_free(waves.first_channels_at_most(8))
-    engine = BatchDirectionalFeatures(pairs, frame_len=args.frame_len, frame_hop=args.frame_hop,
-                                      center=bool(args.center), window=args.window,
-                                      round_power_of_two=bool(args.round_power_of_two))
+    engine = BatchDirectionalFeatures(pairs, **stft_kwargs(args))
     logger.info(f"Compute directional feature with {pairs}")
     total, written, failed = len(waves), 0, 0
     with ArchiveWriter(args.dup_ark, args.scp) as ark:
-        queue = []
 
-        def drain():
+        def flush(queue):
             nonlocal written, failed
-            if not queue:
-                return
             results = engine.run([(samps, mask) for _, samps, mask in queue])
             for (key, _, _), (feats, code) in zip(queue, results):
                 if code:
@@ -66,18 +62,16 @@ def run(args):
                 written += 1
                 if written % 1000 == 0:
                     logger.info(f"Processed {written:d} utterance...")
-            del queue[:]
+            return len(queue)
 
-        for key in waves.index_keys:
-            if key not in masks:
-                logger.warning(f"Missing TF-mask for utterance {key}")
-                continue
-            frames = waves.read_pcm16(key)
-            samps = Pcm16Frames(frames) if frames is not None else waves.read(key)
-            queue.append((key, samps, np.asarray(masks[key])))
-            if len(queue) >= args.batch_utts:
-                drain()
-        drain()
+        def utterances():
+            for key in waves.index_keys:
+                if key not in masks:
+                    logger.warning(f"Missing TF-mask for utterance {key}")
+                    continue
+                yield key, read_samples(waves, key), np.asarray(masks[key])
+
+        run_batches(utterances(), args.batch_utts, flush)
     engine.close()
     logger.info(f"Processed {written:d} utterances over {total:d}")
     if failed:

@@ -13,11 +13,12 @@ Under ``torchrun`` every rank would write the same archive, so the tool runs on 
 import argparse
 
 from setk_amd import _ffi
-from setk_amd.engine import BatchSpatialFeatures, Pcm16Frames
+from setk_amd.engine import BatchSpatialFeatures
 from setk_amd.libs.data_handler import ArchiveWriter, WaveReader
 from setk_amd.libs.opts import StftParser, str2tuple, strtobool
 from setk_amd.libs.spatial import MSC_REASON
 from setk_amd.libs.utils import get_logger
+from setk_amd.sptk._common import read_samples, run_batches, stft_kwargs
 
 logger = get_logger(__name__)
 
@@ -25,27 +26,13 @@ logger = get_logger(__name__)
 def feed(engine, waves, keys, batch_utts, on_result, doa_index=None):
     """Read the utterances `keys` of the wave table, run them through the engine in batches of
     batch_utts and hand (key, features) to on_result in the table's order."""
-    queue = []
-
-    def drain():
-        if not queue:
-            return
+    def flush(queue):
         idx = [doa_index[k] for k, _ in queue] if doa_index is not None else None
         for (key, _), feats in zip(queue, engine.run([s for _, s in queue], doa_index=idx)):
             on_result(key, feats)
-        del queue[:]
+        return len(queue)
 
-    for key in keys:
-        frames = waves.read_pcm16(key)
-        queue.append((key, Pcm16Frames(frames) if frames is not None else waves.read(key)))
-        if len(queue) >= batch_utts:
-            drain()
-    drain()
-
-
-def stft_kwargs(args):
-    return dict(frame_len=args.frame_len, frame_hop=args.frame_hop, center=bool(args.center),
-                window=args.window, round_power_of_two=bool(args.round_power_of_two))
+    run_batches(((key, read_samples(waves, key)) for key in keys), batch_utts, flush)
 
 
 def parse_ipd_pairs(text):

@@ -19,10 +19,11 @@ import argparse
 import numpy as np
 
 from setk_amd import _ffi
-from setk_amd.engine import BatchLocalizer, Pcm16Frames
+from setk_amd.engine import BatchLocalizer
 from setk_amd.libs.data_handler import NumpyReader, WaveReader
 from setk_amd.libs.opts import StftParser, str2tuple
 from setk_amd.libs.utils import get_logger
+from setk_amd.sptk._common import n_fft, read_samples, run_batches, set_torch_free, stft_kwargs
 
 logger = get_logger(__name__)
 
@@ -72,14 +73,10 @@ def run(args):
     if args.backend == "srp":
         srp_pair = parse_srp_pair(args.srp_pair)
         logger.info(f"Choose srp-based algorithm, srp pair is {srp_pair}")
-    n_fft = 2**int(np.ceil(np.log2(args.frame_len))) if args.round_power_of_two else args.frame_len
-    if n_fft == 512:
-        _ffi.set_torch_free(True)  # the engine brings its own buffers and stream
+    set_torch_free(args, None)  # the engine brings its own buffers and stream
     engine = BatchLocalizer(backend=args.backend, steer_vector=steer_vector, srp_pair=srp_pair,
-                            frame_len=args.frame_len, frame_hop=args.frame_hop, center=bool(args.center),
-                            round_power_of_two=bool(args.round_power_of_two), window=args.window,
-                            chunk_len=args.chunk_len if online else -1, look_back=args.look_back)
-    done = 0
+                            chunk_len=args.chunk_len if online else -1, look_back=args.look_back,
+                            **stft_kwargs(args))
     with open(args.doa_scp, "w") as doa_out:
 
         def flush(pending):
@@ -93,18 +90,13 @@ def run(args):
                 doa_out.write(f"{key}\t" + " ".join(f"{d:.4f}" for d in doa) + "\n")
             return len(pending)
 
-        pending = []
-        for key in waves.index_keys:
-            if online:
-                logger.info(f"Processing utterance {key}...")
-            pcm = waves.read_pcm16(key)
-            samps = Pcm16Frames(pcm) if pcm is not None else waves.read(key)
-            pending.append((key, samps, load_mask(readers, key, args.mask_eps, n_fft // 2 + 1)))
-            if len(pending) >= max(1, args.batch_utts):
-                done += flush(pending)
-                pending = []
-        if pending:
-            done += flush(pending)
+        def utterances():
+            for key in waves.index_keys:
+                if online:
+                    logger.info(f"Processing utterance {key}...")
+                yield key, read_samples(waves, key), load_mask(readers, key, args.mask_eps, n_fft(args) // 2 + 1)
+
+        done = run_batches(utterances(), args.batch_utts, flush)
     engine.close()
     logger.info(f"Processing {done} utterance done")
 

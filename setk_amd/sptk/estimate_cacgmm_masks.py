@@ -19,16 +19,18 @@ but nothing holds that for every shape, so the default stays one utterance at a 
 CacgmmTrainer on SpectrogramReader's spectrogram.
 """
 import argparse
-from pathlib import Path
+from contextlib import closing
 
 import numpy as np
 
 from setk_amd import _ffi
 from setk_amd.dist import Shard
 from setk_amd.libs.cluster import CacgmmTrainer, permu_aligner
-from setk_amd.libs.data_handler import NumpyReader, NumpyWriter, ScriptReader, SpectrogramReader
+from setk_amd.libs.data_handler import (NumpyReader, NumpyWriter, ScriptReader, SpectrogramReader,
+                                        WaveReader)
 from setk_amd.libs.opts import StftParser, strtobool
 from setk_amd.libs.utils import get_logger
+from setk_amd.sptk._common import finish, n_fft, num_frames, read_samples, run_batches, stft_kwargs, walk
 
 logger = get_logger(__name__)
 
@@ -58,21 +60,6 @@ def build_parser():
     return parser
 
 
-def _n_fft(args):
-    return 2**int(np.ceil(np.log2(args.frame_len))) if args.round_power_of_two else args.frame_len
-
-
-def _num_frames(reader, key, args):
-    """STFT frames of an utterance from its wave header (librosa's count: 1 + N // hop with
-    centring, 1 + (N - n_fft) // hop without); pipes and globs are decoded for their length."""
-    n = reader.peek_nsamps(key)
-    if n is None:
-        n = reader.read(key).shape[-1]
-    if args.center:
-        return 1 + n // args.frame_hop
-    return 1 + (n - _n_fft(args)) // args.frame_hop
-
-
 def _finish(masks, args):
     """K x F x T posteriors -> what the reference writes (:54-62)."""
     masks = np.transpose(masks, (0, 2, 1))
@@ -93,25 +80,13 @@ def train_table(args, reader, init_reader, shard, dst_dir, write, trainer_cls=Ca
     utterance exactly as the one-process run does.  No draw is made for a key that has an init
     mask, and none under --cgmm-init true with two classes (cluster.py:496)."""
     K = args.num_classes
-    draws = not (args.cgmm_init and K == 2)
-    mine = shard.assign_by_duration(reader)
-    walk = list(reader.index_keys) if (draws and shard.world > 1) else mine
-    own = set(mine)
-    num_bins = _n_fft(args) // 2 + 1
-    # what exists is decided once, before any rank writes: the walk of every rank must skip the
-    # same utterances (the reference does not draw for an utterance it skips, :38)
-    existing = {key for key in walk if (dst_dir / f"{key}.npy").exists()}
-    shard.barrier()
+    num_bins = n_fft(args) // 2 + 1
     num_done = 0
-    for key in walk:
-        if key in existing:
-            if key in own:
-                logger.info(f"Training utterance {key} ... Skip")
-            continue
+    for key, mine in walk(shard, reader, dst_dir, draws=not (args.cgmm_init and K == 2)):
         has_init = bool(init_reader) and key in init_reader
-        if key not in own:
-            if draws and not has_init:
-                np.random.uniform(size=K * num_bins * _num_frames(reader, key, args))
+        if not mine:
+            if not has_init:
+                np.random.uniform(size=K * num_bins * num_frames(reader, key, args, n_fft(args)))
             continue
         stft = reader[key]
         if stft.ndim == 2:
@@ -135,24 +110,15 @@ def train_table(args, reader, init_reader, shard, dst_dir, write, trainer_cls=Ca
 
 def train_batched(args, reader, shard, dst_dir, write):
     """--batch-utts N > 1: waves in, masks out, N utterances per STFT + EM launch."""
-    from setk_amd.engine import CacgmmEstimator, Pcm16Frames
+    from setk_amd.engine import CacgmmEstimator
     K = args.num_classes
     cgmm_init = bool(args.cgmm_init) and K == 2
-    est = CacgmmEstimator(frame_len=args.frame_len, frame_hop=args.frame_hop, center=bool(args.center),
-                          round_power_of_two=True, window=args.window, num_classes=K,
+    est = CacgmmEstimator(**dict(stft_kwargs(args), round_power_of_two=True), num_classes=K,
                           num_iters=args.num_iters, update_alpha=bool(args.update_alpha), cgmm_init=cgmm_init,
                           device=shard.device if shard.world > 1 else None)
-    mine = shard.assign_by_duration(reader)
-    walk = list(reader.index_keys) if (not cgmm_init and shard.world > 1) else mine
-    own = set(mine)
-    existing = {key for key in walk if (dst_dir / f"{key}.npy").exists()}
-    shard.barrier()
-    num_done, pending = 0, []
 
-    def flush():
-        nonlocal num_done
-        if not pending:
-            return
+    def flush(pending):
+        num_done = 0
         starts = None if cgmm_init else [g for _, _, g in pending]
         masks, status = est.estimate([s for _, s, _ in pending], starts, return_status=True)
         for (key, _, _), m, st in zip(pending, masks, status):
@@ -162,34 +128,22 @@ def train_batched(args, reader, shard, dst_dir, write):
             write(key, _finish(np.transpose(m, (0, 2, 1)), args))
             logger.info(f"Training utterance {key} ... Done")
             num_done += 1
-        pending.clear()
+        return num_done
 
-    for key in walk:
-        if key in existing:
-            if key in own:
-                logger.info(f"Training utterance {key} ... Skip")
-            continue
-        T = _num_frames(reader, key, args)
-        g0 = None
-        if not cgmm_init:  # (every rank draws for every utterance it walks; its own are kept)
-            g0 = np.random.uniform(size=[K, est.num_bins, T])
-            if key in own:
-                g0 = g0 / np.sum(g0, 0, keepdims=True)
-                logger.info(f"Random initialized, num_classes = {K}")
-        if key not in own:
-            continue
-        pcm = reader.read_pcm16(key)
-        if pcm is not None:
-            samps = Pcm16Frames(pcm)
-        else:
-            samps = reader.read(key)
-            samps = samps[None] if samps.ndim == 1 else samps
-        pending.append((key, samps, g0))
-        if len(pending) >= args.batch_utts:
-            flush()
-    flush()
-    est.close()
-    return num_done
+    def utterances():
+        for key, mine in walk(shard, reader, dst_dir, draws=not cgmm_init):
+            T = num_frames(reader, key, args, n_fft(args))
+            g0 = None
+            if not cgmm_init:  # (every rank draws for every utterance it walks; its own are kept)
+                g0 = np.random.uniform(size=[K, est.num_bins, T])
+                if mine:
+                    g0 = g0 / np.sum(g0, 0, keepdims=True)
+                    logger.info(f"Random initialized, num_classes = {K}")
+            if mine:
+                yield key, read_samples(reader, key, at_least_2d=True), g0
+
+    with closing(est):
+        return run_batches(utterances(), args.batch_utts, flush)
 
 
 def run(args):
@@ -198,27 +152,19 @@ def run(args):
     np.random.seed(args.seed)
     if not 2 <= args.num_classes <= 4:
         raise _ffi.SetkUnsupported(f"--num-classes {args.num_classes}: the device EM implements 2 .. 4")
-    stft_kwargs = dict(frame_len=args.frame_len, frame_hop=args.frame_hop,
-                       round_power_of_two=args.round_power_of_two, window=args.window,
-                       center=args.center, transpose=False)
-    shard = Shard()
-    dst_dir = Path(args.dst_dir)
-    with NumpyWriter(args.dst_dir) as writer:
-        if args.batch_utts > 1 and _n_fft(args) == 512 and not args.init_mask:
-            from setk_amd.libs.data_handler import WaveReader
-            reader = WaveReader(args.wav_scp)
-            num_done = train_batched(args, reader, shard, dst_dir, writer.write)
-        else:
-            reader = SpectrogramReader(args.wav_scp, **stft_kwargs)
-            MaskReader = {"numpy": NumpyReader, "kaldi": ScriptReader}
-            init_reader = MaskReader[args.fmt](args.init_mask) if args.init_mask else None
-            num_done = train_table(args, reader, init_reader, shard, dst_dir, writer.write)
-    shard.barrier()
-    if shard.world > 1:
-        num_done = int(round(shard.sum_counts([num_done])[0]))
-    if shard.rank == 0:
-        logger.info(f"Train {num_done:d} utterances over {len(reader):d}")
-    shard.close()
+    with closing(Shard()) as shard:
+        with NumpyWriter(args.dst_dir) as writer:
+            if args.batch_utts > 1 and n_fft(args) == 512 and not args.init_mask:
+                reader = WaveReader(args.wav_scp)
+                num_done = train_batched(args, reader, shard, args.dst_dir, writer.write)
+            else:
+                reader = SpectrogramReader(args.wav_scp, frame_len=args.frame_len, frame_hop=args.frame_hop,
+                                           round_power_of_two=args.round_power_of_two, window=args.window,
+                                           center=args.center, transpose=False)
+                MaskReader = {"numpy": NumpyReader, "kaldi": ScriptReader}
+                init_reader = MaskReader[args.fmt](args.init_mask) if args.init_mask else None
+                num_done = train_table(args, reader, init_reader, shard, args.dst_dir, writer.write)
+        finish(shard, num_done, f"Train %d utterances over {len(reader):d}")
 
 
 def main(argv=None):

@@ -12,17 +12,21 @@ numpy's legacy generator exactly as the reference does) and run the general devi
 (libs/cluster.permu_aligner); both take the one-utterance-at-a-time path.
 """
 import argparse
+from contextlib import closing
 from pathlib import Path
 
 import numpy as np
 
 from setk_amd import _ffi
 from setk_amd.dist import Shard
-from setk_amd.engine import CgmmEstimator, Pcm16Frames
+from setk_amd.engine import CgmmEstimator
 from setk_amd.libs.cluster import CgmmTrainer, permu_aligner
-from setk_amd.libs.data_handler import NumpyReader, NumpyWriter, ScriptReader, SpectrogramReader
+from setk_amd.libs.data_handler import (NumpyReader, NumpyWriter, ScriptReader, SpectrogramReader,
+                                        WaveReader)
 from setk_amd.libs.opts import StftParser, strtobool
 from setk_amd.libs.utils import get_logger
+from setk_amd.sptk._common import (finish, n_fft, num_frames as _num_frames, read_samples, run_batches,
+                                   set_torch_free, stft_kwargs, walk)
 
 logger = get_logger(__name__)
 
@@ -56,42 +60,32 @@ def run(args):
     np.random.seed(args.seed)
     if not 2 <= args.num_classes <= 4:
         raise _ffi.SetkUnsupported(f"--num-classes {args.num_classes}: the device EM implements 2 .. 4")
-    stft_kwargs = dict(frame_len=args.frame_len, frame_hop=args.frame_hop,
-                       round_power_of_two=args.round_power_of_two, window=args.window,
-                       center=args.center, transpose=False)
-    shard = Shard()
-    n_fft = 2**int(np.ceil(np.log2(args.frame_len))) if args.round_power_of_two else args.frame_len
-    if n_fft == 512 and not args.init_mask and not args.solve_permu and args.num_classes == 2:
-        return run_batched(args, shard)
-    reader = SpectrogramReader(args.wav_scp, **stft_kwargs)
+    with closing(Shard()) as shard:
+        if n_fft(args) == 512 and not args.init_mask and not args.solve_permu and args.num_classes == 2:
+            num_done, total = run_batched(args, shard)
+        else:
+            num_done, total = run_table(args, shard)
+        finish(shard, num_done, f"Train %d utterances over {total:d}")
+
+
+def run_table(args, shard):
+    """One utterance at a time: CgmmTrainer on SpectrogramReader's spectrogram."""
+    reader = SpectrogramReader(args.wav_scp, frame_len=args.frame_len, frame_hop=args.frame_hop,
+                               round_power_of_two=args.round_power_of_two, window=args.window,
+                               center=args.center, transpose=False)
     MaskReader = {"numpy": NumpyReader, "kaldi": ScriptReader}
     init_reader = MaskReader[args.fmt](args.init_mask) if args.init_mask else None
     num_done = 0
+    num_bins = n_fft(args) // 2 + 1
     with NumpyWriter(args.dst_dir) as writer:
-        dst_dir = Path(args.dst_dir)
-        mine = shard.assign_by_duration(reader)
-        # The K > 2 start comes out of ONE generator that the reference advances utterance by
-        # utterance in table order (estimate_cgmm_masks.py:28, cluster.py:429-434).  With the
-        # table dealt over several ranks every rank walks the whole table and DISCARDS the draws
-        # of the utterances that are not its own (K x F x T doubles each, T from the wave
-        # header), so an 8-GPU run starts every utterance exactly as the one-process run does.
+        # The K > 2 start comes out of the generator that the reference advances utterance by
+        # utterance in table order (estimate_cgmm_masks.py:28, cluster.py:429-434): the walk hands
+        # this rank the other ranks' utterances too, to discard their draws
         # (per utterance: one whose key is missing from --init-mask still draws)
-        random_start = args.num_classes != 2
-        walk = list(reader.index_keys) if (random_start and shard.world > 1) else mine
-        own = set(mine)
-        num_bins = n_fft // 2 + 1
-        # what exists is decided once, before any rank writes: the walk of every rank must skip
-        # the same utterances (the reference does not draw for an utterance it skips, :38)
-        existing = {key for key in walk if (dst_dir / f"{key}.npy").exists()}
-        shard.barrier()
-        for key in walk:
-            if key in existing:
-                if key in own:
-                    logger.info(f"Training utterance {key} ... Skip")
-                continue
-            if key not in own:
+        for key, mine in walk(shard, reader, args.dst_dir, draws=args.num_classes != 2):
+            if not mine:
                 if not (init_reader and key in init_reader):
-                    np.random.uniform(size=args.num_classes * num_bins * _num_frames(reader, key, args, n_fft))
+                    np.random.uniform(size=args.num_classes * num_bins * _num_frames(reader, key, args, n_fft(args)))
                 continue
             stft = reader[key]
             if stft.ndim == 2:
@@ -113,74 +107,38 @@ def run(args):
             # the speech mask for two classes, every class's mask (K x T x F) otherwise (:62-64)
             writer.write(key, (masks[0] if args.num_classes == 2 else masks).astype(np.float32))
             logger.info(f"Training utterance {key} ... Done")
-    shard.barrier()
-    if shard.world > 1:
-        num_done = int(round(shard.sum_counts([num_done])[0]))
-    if shard.rank == 0:
-        logger.info(f"Train {num_done:d} utterances over {len(reader):d}")
-    shard.close()
-
-
-def _num_frames(reader, key, args, n_fft):
-    """STFT frames of an utterance from its wave header (librosa's count: 1 + N // hop with
-    centring, 1 + (N - n_fft) // hop without); pipes and globs are decoded for their length."""
-    n = reader.peek_nsamps(key)
-    if n is None:
-        samps = reader.read(key)
-        n = samps.shape[-1]
-    if args.center:
-        return 1 + n // args.frame_hop
-    return 1 + (n - n_fft) // args.frame_hop
+    return num_done, len(reader)
 
 
 def run_batched(args, shard):
     """Fast path: waves in, masks out, STFT + EM for a batch of utterances on the GPU."""
-    from setk_amd.libs.data_handler import WaveReader
     reader = WaveReader(args.wav_scp)
-    if shard.torch_free_ok:
-        # CgmmEstimator.estimate brings its own buffers and stream: no torch in this process
-        # (bins that fit no resident configuration -- more than 8 channels -- go through torch)
-        _ffi.set_torch_free(reader.first_channels_at_most(8))
-    est = CgmmEstimator(frame_len=args.frame_len, frame_hop=args.frame_hop,
-                        center=bool(args.center), round_power_of_two=True, window=args.window,
+    # CgmmEstimator.estimate brings its own buffers and stream: no torch in this process
+    # (bins that fit no resident configuration -- more than 8 channels -- go through torch)
+    set_torch_free(args, shard, reader.first_channels_at_most(8))
+    est = CgmmEstimator(**dict(stft_kwargs(args), round_power_of_two=True),
                         num_iters=args.num_iters, update_alpha=bool(args.update_alpha),
                         device=shard.device if shard.world > 1 else None)
-    num_done = 0
-    with NumpyWriter(args.dst_dir) as writer:
+    with closing(est), NumpyWriter(args.dst_dir) as writer:
         dst_dir = Path(args.dst_dir)
-        pending = []
 
-        def flush():
-            nonlocal num_done
-            if not pending:
-                return
+        def flush(pending):
             masks = est.estimate([s for _, s in pending])
             for (key, _), m in zip(pending, masks):
                 writer.write(key, m.astype(np.float32))
                 logger.info(f"Training utterance {key} ... Done")
-                num_done += 1
-            pending.clear()
+            return len(pending)
 
-        for key in shard.assign_by_duration(reader):
-            if (dst_dir / f"{key}.npy").exists():
-                logger.info(f"Training utterance {key} ... Skip")
-                continue
-            # one 16-bit PCM file: its frames go up as stored and are converted on the device
-            pcm = reader.read_pcm16(key)
-            if pcm is not None:
-                pending.append((key, Pcm16Frames(pcm)))
-            else:
-                samps = reader.read(key)
-                pending.append((key, samps[None] if samps.ndim == 1 else samps))
-            if len(pending) >= args.batch_utts:
-                flush()
-        flush()
-    shard.barrier()
-    if shard.world > 1:
-        num_done = int(round(shard.sum_counts([num_done])[0]))
-    if shard.rank == 0:
-        logger.info(f"Train {num_done:d} utterances over {len(reader):d}")
-    shard.close()
+        def utterances():
+            for key in shard.assign_by_duration(reader):
+                if (dst_dir / f"{key}.npy").exists():
+                    logger.info(f"Training utterance {key} ... Skip")
+                    continue
+                # one 16-bit PCM file: its frames go up as stored and are converted on the device
+                yield key, read_samples(reader, key, at_least_2d=True)
+
+        num_done = run_batches(utterances(), args.batch_utts, flush)
+    return num_done, len(reader)
 
 
 def main(argv=None):
