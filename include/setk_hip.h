@@ -356,6 +356,15 @@ int setk_cgmm_estimate_batch(setk_handle_t h, int n_utts, int num_channels,
                              const float* const* init_mask, float* const* mask_out, int flags,
                              void* stream);
 
+/* Which kernel form the three entries above run for `num_channels` channels when the longest
+ * utterance of the call has `max_frames` frames: the index of the bin-resident EM's
+ * configuration (cgmm_bin.hip), or -1 for the streaming kernels (cgmm.hip: one bin of that
+ * utterance does not fit a CU, or SETK_CGMM_STREAMING=1; SETK_CGMM_CFG is honoured as by the
+ * dispatcher).  info (may be NULL) receives that configuration's threads per bin, frames per
+ * thread, and how many of those a thread keeps in registers (the others sit in LDS); thread t
+ * owns frames t, t + threads, ...  No handle, no device work. */
+int setk_cgmm_bin_config(int num_channels, int max_frames, int info[3]);
+
 /* ---- CACGMM mask estimation ---------------------------------------------------
  * CacgmmTrainer(obs, K, gamma=gamma0, cgmm_init, update_alpha).train(num_iters) of
  * scripts/sptk/libs/cluster.py:468-535 as used by estimate_cacgmm_masks.py:31-66: the complex

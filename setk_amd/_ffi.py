@@ -236,7 +236,7 @@ def exported_symbols():
         "setk_stft_plan", "setk_stft_num_frames", "setk_istft_num_samples",
         "setk_stft", "setk_stft_batch", "setk_istft", "setk_covar", "setk_pevd", "setk_weights",
         "setk_pcm16_to_float", "setk_pcm16_to_float_batch", "setk_pcm16_channel_stride", "setk_pcm16_deinterleave_batch", "setk_kaldi_cm_decode_batch", "setk_float_to_pcm16", "setk_ban", "setk_rank1", "setk_beamform", "setk_cgmm_masks", "setk_cgmm_masks_k", "setk_cgmm_masks_k_status",
-        "setk_cgmm_masks_batch", "setk_cgmm_estimate_batch", "setk_cacgmm_masks", "setk_cacgmm_estimate_batch", "setk_enhance_batch", "setk_enhance_batch_taps",
+        "setk_cgmm_masks_batch", "setk_cgmm_estimate_batch", "setk_cgmm_bin_config", "setk_cacgmm_masks", "setk_cacgmm_estimate_batch", "setk_enhance_batch", "setk_enhance_batch_taps",
         "setk_apply_weights_batch",
         "setk_directional_feats", "setk_wpe", "setk_wpe_step", "setk_wpe_batch", "setk_wpe_batch_fnt", "setk_wpe_batch_var", "setk_auxiva", "setk_auxiva_batch", "setk_ssl_scores", "setk_ssl_batch", "setk_spatial_feats", "setk_spatial_batch", "setk_ns_gain", "setk_ns_batch", "setk_expint_e1", "setk_set_profiling",
         "setk_last_stage_ms",
@@ -323,6 +323,8 @@ def load_library():
     lib.setk_cgmm_estimate_batch.argtypes = [H, c_int, c_int, POINTER(c_void_p), POINTER(c_int),
                                              c_int, POINTER(c_void_p), POINTER(c_void_p), c_int,
                                              c_void_p]
+    lib.setk_cgmm_bin_config.argtypes = [c_int, c_int, POINTER(c_int)]
+    lib.setk_cgmm_bin_config.restype = c_int
     lib.setk_cacgmm_masks.argtypes = [H, fp, c_int, c_int, c_int, c_int, c_int, fp, c_int, fp, fp, c_void_p]
     lib.setk_cacgmm_estimate_batch.argtypes = [H, c_int, c_int, POINTER(c_void_p), POINTER(c_int), c_int,
                                                c_int, POINTER(c_void_p), c_int, POINTER(c_void_p),
@@ -392,6 +394,15 @@ def host_read_payloads(paths, offsets, nbytes, dsts, threads, mmap_min_bytes):
     if rc != 0:
         raise SetkError(f"setk_host_read_payloads: bad arguments ({rc})")
     return list(S)
+
+
+def cgmm_bin_config(num_channels, max_frames):
+    """setk_cgmm_bin_config: (index, threads, frames per thread, of them in registers) of the
+    bin-resident EM configuration the two-class CGMM entries run for this channel count and
+    longest utterance; (-1, 0, 0, 0) when they run the streaming kernels.  No handle, no device."""
+    info = (c_int * 3)()
+    idx = load_library().setk_cgmm_bin_config(int(num_channels), int(max_frames), info)
+    return (idx, info[0], info[1], info[2]) if idx >= 0 else (-1, 0, 0, 0)
 
 
 def _ptr(x):

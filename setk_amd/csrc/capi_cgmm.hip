@@ -90,6 +90,13 @@ int run_cgmm_bin(setk_handle_t h, int C, int n_utts, const float* const* spec, c
 
 extern "C" {
 
+int setk_cgmm_bin_config(int num_channels, int max_frames, int info[3]) {
+    if (max_frames <= 0 || !cgmm_use_bin(num_channels, max_frames)) return -1;
+    const int cfg = cgmm_bin_config(num_channels, max_frames);
+    if (cfg >= 0 && info) cgmm_bin_config_info(cfg, info);
+    return cfg;
+}
+
 int setk_cgmm_masks_batch(setk_handle_t h, int n_utts, int num_channels,
                           const float* const* spec, const int* num_frames, int num_bins,
                           int num_iters, const float* const* init_mask, float* const* mask_out,

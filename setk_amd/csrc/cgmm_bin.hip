@@ -355,9 +355,10 @@ ZD void write_factor(float* p, const zd lcol, const int i, const int j, const bo
 
 // ---- the solve of one class by one wave -------------------------------------------------
 // exact: reproduce the reference's absolute max(w_max, eps) (initial covariance; bins with
-// near-silent frames).  Otherwise the matrix may carry an arbitrary scale (fast passes drop
-// it) and only relative quantities are used -- equal to the reference's because there
-// lambda_max(R) >= M eps holds by construction (trace(R_eff^-1 R) = M^2, R_eff^-1 <= I / eps).
+// near-silent frames; a covariance whose trace is below M eps).  Otherwise the matrix may
+// carry an arbitrary scale (fast passes drop it) and only relative quantities are used -- equal
+// to the reference's because there lambda_max(R) >= M eps holds by construction
+// (trace(R_eff^-1 R) = M^2, R_eff^-1 <= I / eps) as long as the class keeps sum_t gamma >= eps.
 template <int C, int NT>
 __device__ __noinline__ void solve_class(BinSmem<C, NT>& sm, const int k, const int lane,
                                          const int mode, const int T, const int update_alpha,
@@ -376,7 +377,6 @@ __device__ __noinline__ void solve_class(BinSmem<C, NT>& sm, const int k, const 
     zd* V = sm.V[k];
     zd* W = sm.W[k];
     float* par = sm.par[k];
-    const bool exact = (mode != kModeEm) || sm.tiny;
 
     if (mode == kModeInitId && k == 1) {
         // R = I (cluster.py:423): L = I, log det = 0, eigenvectors = I
@@ -431,6 +431,10 @@ __device__ __noinline__ void solve_class(BinSmem<C, NT>& sm, const int k, const 
 #pragma unroll
         for (int d = 0; d < C; ++d) tr += sm.tot[k][pair_index(d, d, C)] * rd;
     }
+    // A class that has lost its frames (sum_t gamma < eps: the denominator above is the floor, not
+    // the sum) leaves the construction below: lambda_max(R) <= trace(R) can then be less than eps,
+    // where the reference divides by eps instead (cluster.py:107-113) -- exact, like the first pass.
+    const bool exact = (mode != kModeEm) || sm.tiny || tr < (double)C * kEpsD;
     int ex = 0;
     if (tr > 0.0 && tr < 1e300) ex = __builtin_amdgcn_frexp_exp(tr);
     const double scl = __builtin_amdgcn_ldexp(1.0, ex), rscl = __builtin_amdgcn_ldexp(1.0, -ex);
@@ -1108,6 +1112,13 @@ int cgmm_bin_config(int C, int max_frames) {
 int cgmm_bin_threads(int C, int max_frames) {
     const int c = cgmm_bin_config(C, max_frames);
     return c < 0 ? 0 : kCfgs[c].nt;
+}
+
+// threads, frames per thread and frames in registers of configuration `cfg`
+void cgmm_bin_config_info(int cfg, int info[3]) {
+    info[0] = kCfgs[cfg].nt;
+    info[1] = kCfgs[cfg].u;
+    info[2] = kCfgs[cfg].rf;
 }
 
 void cgmm_bin_fill_args(void* out, const float* xb, const float* init_mask, float* gamma_bm, int T,

@@ -245,7 +245,8 @@ np.save(sys.argv[2], m2)
 @pytest.mark.parametrize("C,seconds,iters", [(4, 60.0, 6), (3, 20.0, 5), (7, 12.0, 4)])
 def test_bin_resident_configurations(C, seconds, iters):
     """The other frame-count classes of the bin-resident EM: 60 s (3751 frames: 512 threads x
-    8 frames, two of them in registers), 20 s (1251: 512 x 4), 12 s (751: 256 x 4)."""
+    8 frames, two of them in registers), 20 s (1251: 256 x 8, four in registers), 12 s (751:
+    256 x 4, two in registers) -- what setk_cgmm_bin_config reports for each shape."""
     from setk_amd.engine import CgmmEstimator
     N = int(seconds * 16000)
     mix = o.synth_scene(700 + C, C, N)
