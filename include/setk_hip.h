@@ -710,6 +710,91 @@ int setk_ns_batch(setk_handle_t h, const setk_ns_opts* opts, int n_utts, const v
  * underflows (x > 745). */
 int setk_expint_e1(setk_handle_t h, const double* x, double* y, int n, void* stream);
 
+/* ---- data simulation: scripts/sptk/wav_simulate.py -------------------------
+ * Reverberation, mixing at an SDR / SNR and peak normalisation of far-field training data.
+ * Float32 data, float64 sums and coefficients. */
+#define SETK_SIMU_MAX_TAPS 16384
+#define SETK_SIMU_MAX_CHANNELS 16
+#define SETK_SIMU_REPEAT 0x1 /* setk_simu_source::flags: --point-noise-repeat (:114-118) */
+
+/* add_room_response (wav_simulate.py:29-54, early_energy=False): out[c][n] = sum_j spk[n - j]
+ * rir[c][j], n < num_samples -- scipy.signal.convolve(spk[None], rir)[..., :S] -- as a uniformly
+ * partitioned overlap-save convolution on the 512-point real transform (block 256): exact up to
+ * float32 rounding, worst error about 2e-7 of the peak.
+ *   spk     [num_samples] float32, or int16 with SETK_FLAG_IN_PCM16 (scaled by 2^-15)
+ *   rir     [num_channels][num_taps] float32
+ *   out     [num_channels][num_samples] float32
+ *   power0  NULL, or one float64: np.mean(out[0]**2) (:54), a float64 sum in a fixed order
+ * Buffers may be host or device memory.  1 <= num_channels <= 16, 1 <= num_taps <= 16384,
+ * num_samples >= 1; otherwise SETK_ERR_UNSUPPORTED.  Needs no STFT plan. */
+int setk_fir_reverb(setk_handle_t h, const void* spk, int num_samples, const float* rir, int num_channels,
+                    int num_taps, float* out, double* power0, int flags, void* stream);
+
+/* One source of a mixture: a speaker (add_speaker, :57-93) or a point noise (add_point_noise,
+ * :96-143). */
+typedef struct setk_simu_source {
+    const void* audio;  /* device float32 [channels][num_samples], planar; int16 with
+                         * SETK_FLAG_IN_PCM16.  What read_wav returned: a noise is already cut to
+                         * [offset, offset + mixture length) (:199-205) */
+    const void* rir;    /* device float32 [rir_channels][rir_taps], or NULL (the close-talk forms:
+                         * the source itself is the image, :69-72, :120-124) */
+    int num_samples;
+    int channels;       /* 1 with a RIR (:38-39) */
+    int rir_channels, rir_taps;
+    int begin;          /* --src-begin / --point-noise-begin, >= 0 */
+    int flags;          /* SETK_SIMU_REPEAT (noises) */
+    double snr;         /* --src-sdr of a speaker against the first (ignored for the first, :91),
+                         * --point-noise-snr of a noise */
+} setk_simu_source;
+
+/* One mixture: the arguments of run_simu (:166-312) after its files are read. */
+typedef struct setk_simu_recipe {
+    const setk_simu_source* speakers; /* host array [n_speakers], n_speakers >= 1 */
+    const setk_simu_source* noises;   /* host array [n_noises] or NULL */
+    int n_speakers, n_noises;
+    const void* iso;      /* NULL, or the isotropic noise cut to [offset, offset + mixture length):
+                           * device [iso_channels][iso_samples], planar, same sample type as audio.
+                           * Channel 0 of it is added to EVERY channel (:293-302) */
+    int iso_samples, iso_channels;
+    double iso_snr;
+    int dump_channel;     /* --dump-channel: >= 0 takes that channel of every RIR (:77-79) */
+    int pad_;
+    double norm_factor;   /* --norm-factor */
+    /* results (device memory) */
+    void* mix;              /* float32 [N][L], or with SETK_FLAG_OUT_PCM16 int16 [L][N], the frames of a
+                             * wave file; N = setk_simu_num_channels, L = setk_simu_num_samples */
+    void* const* spk_ref;   /* host array [n_speakers]: channel 0 of every scaled speaker image, [L]
+                             * float32 or int16 (:307); an entry may be NULL */
+    void* noise_ref;        /* channel 0 of the scaled noise, [L] (:309-312), or NULL.  Not written
+                             * when the recipe has neither point nor isotropic noise */
+} setk_simu_recipe;
+
+/* L = max_i(begin_i + size_i) (:195; `size` counts the samples of every channel) and N, the
+ * channels of the first speaker's image; negative SETK_ERR_* for a recipe without speakers. */
+int setk_simu_num_samples(const setk_simu_recipe* r);
+int setk_simu_num_channels(const setk_simu_recipe* r);
+
+/* run_simu (:244-312) for a ragged batch of mixtures -- length, source count, tap count and
+ * channel count differ freely -- in a handful of launches: the transforms of all sources and RIRs
+ * (a RIR that several sources of the call share is transformed once), the convolutions, the image
+ * powers, the coefficients (coeff_snr, :17-26, EPSILON inside), the speaker-only power (:255), the
+ * peak max |mix| (:304, an integer maximum on the float64 bits) and the scaled outputs.  Sums run in
+ * a fixed order: two runs, and a mixture alone or inside any batch, give the same bits.
+ *   status[u]  host or device, or NULL: SETK_NUM_NONFINITE when NaN / inf reached the mixture
+ * flags: SETK_FLAG_IN_PCM16 (every audio / iso buffer is int16) | SETK_FLAG_OUT_PCM16 (libsndfile's
+ * float -> PCM_16 on float32(value), what write_wav does, libs/utils.py:45-62).
+ * What the reference's numpy refuses is SETK_ERR_INVALID with its reason: a multi-channel source
+ * with a RIR, images whose channel counts cannot be broadcast, noise against speaker channels,
+ * isotropic channels, and point noises whose durations do not fit the LAST noise's (:110-142 mix
+ * every noise over the duration left behind by the first loop).  Limits (SETK_ERR_UNSUPPORTED): 1 to
+ * 16 channels, RIRs of at most 16384 taps, at least one sample per source, begin >= 0.  A recipe
+ * without RIRs runs the mixing only.  Scratch comes from the handle's arena; the call returns
+ * when the work has run.  With setk_set_profiling the stage times of setk_last_stage_ms are
+ * out[0] transforms, out[1] convolutions, out[2] powers, coefficients and peak, out[3] scaling
+ * and rounding. */
+int setk_simu_batch(setk_handle_t h, int n_mix, const setk_simu_recipe* recipes, int* status, int flags,
+                    void* stream);
+
 /* ---- fused hot path ------------------------------------------------------
  * The compute body of apply_adaptive_beamformer.py:130-178 for a batch of
  * utterances that share the channel count, in four kernel stages:

@@ -172,6 +172,65 @@ def ns_opts(kind, eps=1e-7, gain=True, spec=False, w_mcra=None, w_local=None, w_
     return o
 
 
+SIMU_REPEAT = 1
+SIMU_MAX_TAPS, SIMU_MAX_CHANNELS = 16384, 16
+
+
+class SimuSource(ctypes.Structure):
+    _fields_ = [("audio", c_void_p), ("rir", c_void_p), ("num_samples", c_int), ("channels", c_int),
+                ("rir_channels", c_int), ("rir_taps", c_int), ("begin", c_int), ("flags", c_int),
+                ("snr", ctypes.c_double)]
+
+
+class SimuRecipe(ctypes.Structure):
+    _fields_ = [("speakers", POINTER(SimuSource)), ("noises", POINTER(SimuSource)), ("n_speakers", c_int),
+                ("n_noises", c_int), ("iso", c_void_p), ("iso_samples", c_int), ("iso_channels", c_int),
+                ("iso_snr", ctypes.c_double), ("dump_channel", c_int), ("pad_", c_int),
+                ("norm_factor", ctypes.c_double), ("mix", c_void_p), ("spk_ref", POINTER(c_void_p)),
+                ("noise_ref", c_void_p)]
+
+
+def simu_source(audio, num_samples, channels=1, rir=None, rir_channels=0, rir_taps=0, begin=0, snr=0.0,
+                repeat=False):
+    """setk_simu_source: audio / rir are device addresses (planar channels)."""
+    return SimuSource(audio=audio, rir=rir, num_samples=int(num_samples), channels=int(channels),
+                      rir_channels=int(rir_channels), rir_taps=int(rir_taps), begin=int(begin),
+                      flags=SIMU_REPEAT if repeat else 0, snr=float(snr))
+
+
+def simu_recipe(speakers, noises=(), iso=None, iso_samples=0, iso_channels=0, iso_snr=0.0, dump_channel=-1,
+                norm_factor=0.9):
+    """setk_simu_recipe over lists of simu_source; the outputs (mix, spk_ref, noise_ref) are set with
+    simu_recipe_outputs once the caller knows the sizes.  The structure keeps its tables alive."""
+    r = SimuRecipe(n_speakers=len(speakers), n_noises=len(noises), iso=iso, iso_samples=int(iso_samples),
+                   iso_channels=int(iso_channels), iso_snr=float(iso_snr), dump_channel=int(dump_channel),
+                   norm_factor=float(norm_factor))
+    r._speakers = (SimuSource * max(len(speakers), 1))(*speakers)
+    r.speakers = ctypes.cast(r._speakers, POINTER(SimuSource))
+    if len(noises):
+        r._noises = (SimuSource * len(noises))(*noises)
+        r.noises = ctypes.cast(r._noises, POINTER(SimuSource))
+    r._refs = (c_void_p * max(len(speakers), 1))()
+    r.spk_ref = ctypes.cast(r._refs, POINTER(c_void_p))
+    return r
+
+
+def simu_recipe_outputs(r, mix, spk_refs, noise_ref=None):
+    r.mix = mix
+    for i, p in enumerate(spk_refs):
+        r._refs[i] = p
+    r.noise_ref = noise_ref
+
+
+def simu_shape(r):
+    """(channels N, samples L) of a recipe's mixture; no handle, no device."""
+    lib = load_library()
+    N, L = lib.setk_simu_num_channels(ctypes.byref(r)), lib.setk_simu_num_samples(ctypes.byref(r))
+    if N < 0 or L < 0:
+        raise ValueError("a recipe needs at least one speaker")
+    return N, L
+
+
 class SetkError(RuntimeError):
     pass
 
@@ -238,7 +297,7 @@ def exported_symbols():
         "setk_pcm16_to_float", "setk_pcm16_to_float_batch", "setk_pcm16_channel_stride", "setk_pcm16_deinterleave_batch", "setk_kaldi_cm_decode_batch", "setk_float_to_pcm16", "setk_ban", "setk_rank1", "setk_beamform", "setk_cgmm_masks", "setk_cgmm_masks_k", "setk_cgmm_masks_k_status",
         "setk_cgmm_masks_batch", "setk_cgmm_estimate_batch", "setk_cgmm_bin_config", "setk_cacgmm_masks", "setk_cacgmm_estimate_batch", "setk_enhance_batch", "setk_enhance_batch_taps",
         "setk_apply_weights_batch",
-        "setk_directional_feats", "setk_wpe", "setk_wpe_step", "setk_wpe_batch", "setk_wpe_batch_fnt", "setk_wpe_batch_var", "setk_auxiva", "setk_auxiva_batch", "setk_ssl_scores", "setk_ssl_batch", "setk_spatial_feats", "setk_spatial_batch", "setk_ns_gain", "setk_ns_batch", "setk_expint_e1", "setk_set_profiling",
+        "setk_directional_feats", "setk_wpe", "setk_wpe_step", "setk_wpe_batch", "setk_wpe_batch_fnt", "setk_wpe_batch_var", "setk_auxiva", "setk_auxiva_batch", "setk_ssl_scores", "setk_ssl_batch", "setk_spatial_feats", "setk_spatial_batch", "setk_ns_gain", "setk_ns_batch", "setk_expint_e1", "setk_fir_reverb", "setk_simu_num_samples", "setk_simu_num_channels", "setk_simu_batch", "setk_set_profiling",
         "setk_last_stage_ms",
         "setk_comm_unique_id", "setk_comm_create", "setk_comm_allreduce_f64", "setk_comm_barrier",
         "setk_comm_destroy", "setk_comm_last_error", "setk_host_read_payloads"
@@ -363,6 +422,10 @@ def load_library():
     lib.setk_ns_batch.argtypes = [H, POINTER(NsOpts), c_int, POINTER(c_void_p), POINTER(c_int), POINTER(c_void_p),
                                   POINTER(c_void_p), fp, c_int, c_void_p]
     lib.setk_expint_e1.argtypes = [H, fp, fp, c_int, c_void_p]
+    lib.setk_fir_reverb.argtypes = [H, fp, c_int, fp, c_int, c_int, fp, fp, c_int, c_void_p]
+    lib.setk_simu_num_samples.argtypes = [POINTER(SimuRecipe)]
+    lib.setk_simu_num_channels.argtypes = [POINTER(SimuRecipe)]
+    lib.setk_simu_batch.argtypes = [H, c_int, POINTER(SimuRecipe), fp, c_int, c_void_p]
     lib.setk_directional_feats.argtypes = [H, fp, fp, POINTER(c_int), c_int, c_int, c_int, c_int,
                                            fp, c_void_p]
     lib.setk_apply_weights_batch.argtypes = [
@@ -979,6 +1042,23 @@ class Context:
         n = x.size if isinstance(x, np.ndarray) else x.numel()
         self.check(self._lib.setk_expint_e1(self._h, _ptr(x), _ptr(y), int(n),
                                             current_stream_ptr() if stream is None else stream))
+
+    def fir_reverb(self, spk, S, rir, N, R, out, power0=None, flags=0, stream=None):
+        """add_room_response: spk [S] float32 (int16 with FLAG_IN_PCM16), rir [N][R] float32 -> out
+        [N][S] float32 and, when asked, power0 float64[1] = mean(out[0]**2) (numpy arrays, device
+        tensors or device addresses)."""
+        self.check(
+            self._lib.setk_fir_reverb(self._h, _ptr(spk), int(S), _ptr(rir), int(N), int(R), _ptr(out), _ptr(power0),
+                                      int(flags), current_stream_ptr() if stream is None else stream))
+
+    def simu_batch(self, recipes, status=None, flags=0, stream=None):
+        """run_simu for a list of simu_recipe structures (device buffers in and out); status int32[n]
+        (numpy or device address) or None."""
+        n = len(recipes)
+        R = (SimuRecipe * n)(*recipes)
+        self.check(
+            self._lib.setk_simu_batch(self._h, n, R, _ptr(status), int(flags),
+                                      current_stream_ptr() if stream is None else stream))
 
     def set_profiling(self, on):
         self.check(self._lib.setk_set_profiling(self._h, 1 if on else 0))

@@ -378,4 +378,58 @@ bool ns_supported(int F);
 hipError_t launch_ns(const NsUtt* d_utts, const NsParams* d_params, int kind, int n_utts, int F, hipStream_t s);
 hipError_t launch_expint_e1(const double* x, double* y, int n, hipStream_t s);
 
+// Data simulation (simu.hip): partitioned overlap-save reverberation on the 512-point transform,
+// block 256, spectra in the transform's lane layout (256 complex64 per transform), and the mixing.
+constexpr int kSimuBlock = 256;
+constexpr int kSimuMaxTaps = 16384;    // = SETK_SIMU_MAX_TAPS
+constexpr int kSimuMaxChannels = 16;   // = SETK_SIMU_MAX_CHANNELS
+constexpr int kSimuPowChunk = 8192;    // samples per partial sum
+struct SimuFwd {      // a run of forward transforms of one signal
+    const void* src;  // float32 or (fmt) int16
+    float2* X;        // [frames][256]
+    int fmt, len;     // kAudioF32 | kAudioPcm16; samples behind src
+    int n;            // samples taken (beyond them zeros); wrap: sample i is src[i % len]
+    int wrap, frames;
+    int rir;          // 1: frame p is RIR block p (256 samples, 256 zeros); 0: source frame k
+};
+struct SimuItem { int job, f0; };  // 16 transforms from f0
+struct SimuConv {
+    const float2* X;  // [K][256]
+    const float2* H;  // [N][P][256]
+    float* out;       // [N][S]
+    int K, P, N, S;
+};
+struct SimuConvItem { int job, k0, c0, pad_; };  // 16 frames from k0, the kernel's channels from c0
+struct SimuImage {     // one image of a mixture: a reverberated source, or the source itself
+    const void* data;  // [nch][pitch]
+    int fmt, len, pitch, nch;
+    int beg, dur;      // mixed into [beg, beg + dur); sample i >= len is data[i % len]
+    int pw_n;          // the mean square of channel 0 runs over [0, pw_n)
+    int part0, nparts; // its partial sums
+    int pad_;
+    double snr;
+};
+struct SimuMix {
+    const SimuImage* img;  // speakers, point noises, the isotropic chunk
+    double* coeff;         // [n_img]
+    double* power;         // [n_img + 1]: the images', the speaker-only mixture's
+    double* spk_partial;   // [ceil(L / kSimuPowChunk)]
+    unsigned long long* peak;  // the bits of max |mix| (float64)
+    int* status;
+    void* mix;             // float32 [N][L] or int16 [L][N]
+    void* noise_ref;       // [L] or null
+    void* const* spk_ref;  // [n_spk] -> [L] (entries may be null)
+    double norm_factor;
+    int n_spk, n_img, N, L;
+};
+int simu_conv_channels(int N);
+hipError_t launch_simu_fwd(const SimuFwd* d_jobs, const SimuItem* d_items, int n_items, hipStream_t s);
+hipError_t launch_simu_conv(const SimuConv* d_jobs, const SimuConvItem* d_items, int nc, int n_items, hipStream_t s);
+hipError_t launch_simu_power(const SimuImage* d_imgs, int n_imgs, int max_n, double* d_partial, hipStream_t s);
+hipError_t launch_simu_coeff(const SimuMix* d_mixes, int n_mix, int stage, const double* d_partial, hipStream_t s);
+hipError_t launch_simu_spkpow(const SimuMix* d_mixes, int n_mix, int max_len, hipStream_t s);
+hipError_t launch_simu_peak(const SimuMix* d_mixes, int n_mix, int max_channels, int max_len, hipStream_t s);
+hipError_t launch_simu_out(const SimuMix* d_mixes, int n_mix, int max_channels, int max_len, bool pcm16,
+                           hipStream_t s);
+
 }  // namespace setk

@@ -15,3 +15,4 @@ from .ssl import BatchLocalizer  # noqa: F401
 from .directional import BatchDirectionalFeatures  # noqa: F401
 from .spatial import BatchSpatialFeatures  # noqa: F401
 from .ns import BatchNoiseSuppressor  # noqa: F401
+from .simu import BatchSimulator  # noqa: F401

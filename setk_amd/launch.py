@@ -10,7 +10,8 @@ attempt ends with a non-zero status -- a rank raised, was killed, lost its GPU: 
 the other ranks down with it -- the job is started again with `--skip-existing true --requeue
 true`: finished wave files are complete by construction (written to `{key}.wav.part`, renamed
 when closed), so the new attempt finds what is missing and deals ONLY that over all ranks.
-The command lines that take these two flags: apply_adaptive_beamformer.py, apply_ns.py.
+The command lines that take these two flags: apply_adaptive_beamformer.py, apply_ns.py, wav_simulate.py
+(with --cmd-list).
 """
 import argparse
 import os
