@@ -805,8 +805,15 @@ int setk_simu_batch(setk_handle_t h, int n_mix, const setk_simu_recipe* recipes,
  * audio[u]   device float32 [C][num_samples[u]]; with SETK_FLAG_IN_PCM16 device int16
  *            [C][setk_pcm16_channel_stride(num_samples[u])] (cast to const float*).
  *            Float samples of any magnitude are accepted: the matrix-core transforms of
- *            stage 3 bring an utterance whose max |x| exceeds 1 into their fp16 operand range
- *            by a power of two taken from stage 1's max |x| (exact, undone on the way out)
+ *            stage 3 bring an utterance whose max |x| exceeds 1, or stays below 2^-15, into
+ *            their fp16 operand range by a power of two taken from stage 1's max |x| (exact,
+ *            undone on the way out; nothing changes for 2^-15 <= max |x| <= 1).  Two limits:
+ *            stage 1's covariances are float32, so |X|^2 must stay finite (max |x| up to about
+ *            2^50; beyond it the utterance is reported SETK_NUM_NONFINITE); and the opt-in
+ *            matrix-core stage 1 (SETK_MC_PASS1=1) has no such power of two -- it is meant for
+ *            max |x| <= 1, reports SETK_NUM_NONFINITE where a sum leaves fp16 above that, and
+ *            below 2^-15 its covariances carry the absolute fp16 floor (2^-34 of full scale per
+ *            sample; measured figures in tests/PARITY_NOTES_STFT.md)
  * mask_s[u]  device float32 [T_u][F]
  * mask_n     NULL, or per-utterance interferer masks (--itf-mask)
  * wave[u]    device float32 (or int16) [hop*(T_u-1)] when center, see

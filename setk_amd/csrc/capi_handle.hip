@@ -339,7 +339,18 @@ int setk_stream_create(setk_handle_t h, void** out) {
 
 int setk_stream_destroy(setk_handle_t h, void* stream) {
     if (!h) return SETK_ERR_INVALID;
+    // The arena remembers the stream of the handle's last call and drains it when the next call
+    // comes on another one (arena_reset).  A destroyed stream must not stay remembered: the next
+    // call would synchronise a dangling hipStream_t.  Drain it here instead.
+    hipError_t drained = hipSuccess;
+    if (stream && h->have_last_stream && h->last_stream == static_cast<hipStream_t>(stream)) {
+        drained = hipStreamSynchronize(h->last_stream);
+        h->have_last_stream = false;
+        h->last_stream = nullptr;
+    }
+    // (destroyed whatever the drain said: an error there must not leak the stream)
     if (stream) HIP_TRY(h, hipStreamDestroy(static_cast<hipStream_t>(stream)));
+    HIP_TRY(h, drained);
     return SETK_OK;
 }
 

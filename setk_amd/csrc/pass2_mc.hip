@@ -133,15 +133,22 @@ __global__ __launch_bounds__(p2mc_threads(PCM), kP2McWavesPerSimd) void beamform
     // it into norm_bits before this kernel started): samples above 1 -- float wave files, int16
     // ranges handed over as floats (WaveReader(normalize=False)), C-API callers -- are brought
     // into range by the power of two 2^-e in the window rows and taken out again by 2^e in the
-    // synthesis rows.  e = 0 (nothing changes, bit for bit) whenever max |x| <= 1.  The
-    // beamformer is linear, every other stage of this kernel is scale free (the inverse
-    // transform normalises each frame's spectrum by its own power of two).  16-bit PCM arrives
-    // as integers: 2^-15 on the way in, nothing on the way out.
+    // synthesis rows.  The other way round for an utterance that is quiet throughout: below
+    // 2^-10 of full scale the lo halves of the splits go subnormal (an absolute floor of 2^-34
+    // per sample, mcdft.h), so max |x| < 2^-15 -- less than one step of 16-bit PCM, float input
+    // only -- is lifted by the same exact power of two (tests/stft_cases.py `quiet`: without it
+    // the wave of an utterance peaking at 2^-24 came out 6e-4 off, at 2^-32 0.15, against the
+    // 1e-3 waveform bar; with it 2e-7).  e = 0 (nothing changes, bit for bit)
+    // whenever 2^-15 <= max |x| <= 1, and for silence.  The beamformer is linear, every other
+    // stage of this kernel is scale free (the inverse transform normalises each frame's
+    // spectrum by its own power of two).  16-bit PCM arrives as integers: 2^-15 on the way in,
+    // nothing on the way out.
     float in_sc = PCM ? 3.0517578125e-05f : 1.f, out_sc = 1.f;
     if (a.norm_bits) {
         const unsigned nb = a.norm_bits[wi.utt];  // max |x| (natural units) as float bits
+        const float mx = __builtin_bit_cast(float, nb);
         int e = (int)((nb >> 23) & 0xff) - 126;   // max |x| < 2^e
-        e = (__builtin_bit_cast(float, nb) <= 1.f) ? 0 : (e > 100 ? 100 : e);
+        e = (mx > 1.f) ? (e > 100 ? 100 : e) : (mx > 0.f && mx < 3.0517578125e-05f) ? (e < -100 ? -100 : e) : 0;
         in_sc *= __builtin_bit_cast(float, (unsigned)(127 - e) << 23);
         out_sc = __builtin_bit_cast(float, (unsigned)(127 + e) << 23);
     }

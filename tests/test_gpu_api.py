@@ -740,3 +740,27 @@ def test_cli_strict_reference_skips_what_the_reference_skips(tmp_path):
     for gevd_dir in ("gev",):
         files, err = run(f"{td}/{gevd_dir}", "--strict-reference", "true", "--beamformer", "gevd")
         assert len(files) == 4 and "Raise linalg error" not in err   # the reference's GEV never raises
+
+
+def test_a_destroyed_stream_is_forgotten_by_the_handle():
+    """The handle drains the stream of its last call when the next call comes on another one.  A
+    stream created through the handle, used for a call and destroyed must not stay remembered:
+    the next call, on another stream, runs and gives the same result."""
+    from setk_amd import _ffi
+    c = _ffi.Context(0)
+    try:
+        c.stft_plan(512, 256, 512, True)
+        x = o.synth_utterance(5, 2, 6000)
+        outs = [np.full((2, c.num_frames(6000), 257), np.nan, np.complex64) for _ in range(3)]
+        for k in range(2):
+            s = c.stream_create()
+            c.stft(x, outs[k], stream=s)
+            c.stream_destroy(s)
+            # (other streams come and go: the freed one's memory is handed out again)
+            for t in [c.stream_create() for _ in range(4)]:
+                c.stream_destroy(t)
+        c.stft(x, outs[2], stream=0)
+        assert np.array_equal(outs[0], outs[1]) and np.array_equal(outs[0], outs[2])
+        assert np.isfinite(outs[2]).all()
+    finally:
+        c.close()
