@@ -439,7 +439,7 @@ int setk_apply_weights_batch(setk_handle_t h, int n_utts, int num_channels,
  * SETK_NUM_SINGULAR is numpy's LinAlgError, SETK_NUM_RANKDEF a note (columns at the noise
  * level were dropped; the result is finite).  Limits: channels <= 16, NK = channels * taps
  * <= 256.  While R fits LDS (NK^2 + NK N + 16 (NK + N) complex128 <= 160 KB: up to 8
- * channels x 10 taps, 16 x 4) a workgroup never leaves its CU; beyond that (8 x 12, 16 x 6,
+ * channels x 11 taps, 16 x 5) a workgroup never leaves its CU; beyond that (8 x 12, 16 x 6,
  * 16 x 10 ...) R is factored in global scratch of the handle's arena (NK^2 complex128 per
  * bin and utterance in flight).  NK > 256: SETK_ERR_UNSUPPORTED names the bound. */
 int setk_wpe(setk_handle_t h, const float* spec, int num_channels, int num_frames,
@@ -481,6 +481,14 @@ int setk_wpe_batch_var(setk_handle_t h, int n_utts, const float* const* spec, in
 int setk_wpe_batch_fnt(setk_handle_t h, int n_utts, const float* const* spec, int num_channels,
                        const int* num_frames, int num_bins, int taps, int delay, int context,
                        int num_iters, float* const* out, int* status, void* stream);
+
+/* Which form of the step kernel the entries above launch for `num_channels` x `taps`: *wide is 1
+ * when R is factored in global scratch and 0 when it stays in LDS, *tiles_per_wave the
+ * accumulator tiles per wavefront of the kernel instantiation (the wide form: per pass over the
+ * frames), *chunk_frames how many frames are staged at a time (64, 32 or 16).  Any of the three
+ * may be NULL.  SETK_ERR_UNSUPPORTED for a shape the entries refuse.  No handle, no device
+ * work. */
+int setk_wpe_form(int num_channels, int taps, int* wide, int* tiles_per_wave, int* chunk_frames);
 
 /* ---- AuxIVA blind source separation (scripts/sptk/apply_auxiva.py) ----------
  * auxiva(X, epochs) (:24-57): as many sources as channels, demixing matrices W_f = I to start

@@ -297,7 +297,7 @@ def exported_symbols():
         "setk_pcm16_to_float", "setk_pcm16_to_float_batch", "setk_pcm16_channel_stride", "setk_pcm16_deinterleave_batch", "setk_kaldi_cm_decode_batch", "setk_float_to_pcm16", "setk_ban", "setk_rank1", "setk_beamform", "setk_cgmm_masks", "setk_cgmm_masks_k", "setk_cgmm_masks_k_status",
         "setk_cgmm_masks_batch", "setk_cgmm_estimate_batch", "setk_cgmm_bin_config", "setk_cacgmm_masks", "setk_cacgmm_estimate_batch", "setk_enhance_batch", "setk_enhance_batch_taps",
         "setk_apply_weights_batch",
-        "setk_directional_feats", "setk_wpe", "setk_wpe_step", "setk_wpe_batch", "setk_wpe_batch_fnt", "setk_wpe_batch_var", "setk_auxiva", "setk_auxiva_batch", "setk_ssl_scores", "setk_ssl_batch", "setk_spatial_feats", "setk_spatial_batch", "setk_ns_gain", "setk_ns_batch", "setk_expint_e1", "setk_fir_reverb", "setk_simu_num_samples", "setk_simu_num_channels", "setk_simu_batch", "setk_set_profiling",
+        "setk_directional_feats", "setk_wpe", "setk_wpe_step", "setk_wpe_batch", "setk_wpe_batch_fnt", "setk_wpe_batch_var", "setk_wpe_form", "setk_auxiva", "setk_auxiva_batch", "setk_ssl_scores", "setk_ssl_batch", "setk_spatial_feats", "setk_spatial_batch", "setk_ns_gain", "setk_ns_batch", "setk_expint_e1", "setk_fir_reverb", "setk_simu_num_samples", "setk_simu_num_channels", "setk_simu_batch", "setk_set_profiling",
         "setk_last_stage_ms",
         "setk_comm_unique_id", "setk_comm_create", "setk_comm_allreduce_f64", "setk_comm_barrier",
         "setk_comm_destroy", "setk_comm_last_error", "setk_host_read_payloads"
@@ -401,6 +401,8 @@ def load_library():
     lib.setk_wpe_batch.argtypes = [H, c_int, POINTER(c_void_p), c_int, POINTER(c_int), c_int, c_int,
                                    c_int, c_int, c_int, POINTER(c_void_p), fp, c_void_p]
     lib.setk_wpe_batch_fnt.argtypes = lib.setk_wpe_batch.argtypes
+    lib.setk_wpe_form.argtypes = [c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int)]
+    lib.setk_wpe_form.restype = c_int
     lib.setk_host_read_payloads.argtypes = [c_int, POINTER(ctypes.c_char_p), POINTER(ctypes.c_longlong),
                                             POINTER(ctypes.c_longlong), POINTER(c_void_p), c_int,
                                             ctypes.c_longlong, POINTER(c_int)]
@@ -466,6 +468,15 @@ def cgmm_bin_config(num_channels, max_frames):
     info = (c_int * 3)()
     idx = load_library().setk_cgmm_bin_config(int(num_channels), int(max_frames), info)
     return (idx, info[0], info[1], info[2]) if idx >= 0 else (-1, 0, 0, 0)
+
+
+def wpe_form(num_channels, taps):
+    """setk_wpe_form: (wide, tiles per wavefront, frames per staged chunk) of the step kernel the
+    WPE entries launch for this shape; None for a shape they refuse.  No handle, no device."""
+    w, n, tc = c_int(), c_int(), c_int()
+    rc = load_library().setk_wpe_form(int(num_channels), int(taps), ctypes.byref(w), ctypes.byref(n),
+                                      ctypes.byref(tc))
+    return (bool(w.value), n.value, tc.value) if rc == SETK_OK else None
 
 
 def _ptr(x):

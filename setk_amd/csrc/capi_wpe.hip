@@ -151,6 +151,12 @@ int wpe_batch_impl(setk_handle_t h, int n_utts, const float* const* spec, int nu
 
 extern "C" {
 
+int setk_wpe_form(int num_channels, int taps, int* wide, int* tiles_per_wave, int* chunk_frames) {
+    if (!wpe_supported(num_channels, taps)) return SETK_ERR_UNSUPPORTED;
+    wpe_form(num_channels, taps, wide, tiles_per_wave, chunk_frames);
+    return SETK_OK;
+}
+
 int setk_wpe(setk_handle_t h, const float* spec, int num_channels, int num_frames, int num_bins,
              int taps, int delay, int context, int num_iters, const float* lambda_enh,
              float* out, float* inv_lambda_out, int* status, void* stream) {

@@ -254,6 +254,9 @@ void wpe_fill_args(void* dst, const float* x_fct, const double* lam, float* out_
 size_t wpe_wide_bytes_per_bin(int N, int taps);
 hipError_t launch_wpe_step_batch(const void* d_tbl, int n_utts, int N, int F, int taps,
                                  hipStream_t s);
+// what launch_wpe_step_batch picks for a supported shape (host only): R in global memory?,
+// accumulator tiles per wavefront of the instantiation, frames per staged chunk
+void wpe_form(int N, int taps, int* wide, int* tiles_per_wave, int* chunk_frames);
 
 // CACGMM (cacgmm.hip): one launch runs the whole EM of every (bin, utterance); observations
 // [F][C][Tp] complex64 with Tp = cacgmm_pitch(T), work area cacgmm_work_bytes per utterance

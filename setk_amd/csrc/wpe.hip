@@ -473,7 +473,7 @@ bool wpe_supported(int N, int taps) {
 }
 
 // what exactly a shape is refused for (R itself moves to global memory when it does not fit
-// LDS -- 8 channels x 11 taps, 16 x 5 and up; the bound that remains is NK <= 256)
+// LDS -- 8 channels x 12 taps, 16 x 6 and up; the bound that remains is NK <= 256)
 const char* wpe_limit_message(int N, int taps) {
     static thread_local char buf[256];
     const int NK = N * taps;
@@ -538,22 +538,34 @@ void wpe_fill_args(void* dst, const float* x_fct, const double* lam, float* out_
     memcpy(dst, &a, sizeof(a));
 }
 
+// the instantiations of the LDS form, by tiles per wavefront (no supported shape needs 6)
+constexpr int kWpeNTW[] = {1, 2, 3, 4, 5, 8, 10, 12, 14, 17, 20, 23, 26};
+
+// which kernel a shape runs: the wide form with kWpeWideNTW tiles per wavefront and pass, or
+// the smallest LDS instantiation that holds its ceil(NT / 4) tiles (0: none does)
+int wpe_tiles_per_wave(int N, int taps) {
+    if (wpe_is_wide(N, taps)) return kWpeWideNTW;
+    const int RT = (N * taps + 7) / 8, XT = (N + 7) / 8;
+    const int ntw = (RT * (RT + 1) / 2 + RT * XT + 3) / 4;  // <= 26
+    for (int n : kWpeNTW)
+        if (ntw <= n) return n;
+    return 0;
+}
+
 // d_tbl: n_utts argument blocks (device); every utterance has N channels and `taps` taps
 hipError_t launch_wpe_step_batch(const void* d_tbl, int n_utts, int N, int F, int taps,
                                  hipStream_t s) {
     const size_t lds = wpe_lds_bytes(N, taps);
     void (*kern)(const WpeArgs*, int) = nullptr;
-    const int RT = (N * taps + 7) / 8, XT = (N + 7) / 8;
-    const int ntw = (RT * (RT + 1) / 2 + RT * XT + 3) / 4;  // tiles per wavefront, <= 26
+    const int ntw = wpe_tiles_per_wave(N, taps);
     if (wpe_is_wide(N, taps)) kern = wpe_step_kernel<kWpeWideNTW, true>;
 #define SETK_WPE_CASE(n) \
-    if (!kern && ntw <= n) kern = wpe_step_kernel<n, false>
+    if (!kern && ntw == n) kern = wpe_step_kernel<n, false>
     SETK_WPE_CASE(1);
     SETK_WPE_CASE(2);
     SETK_WPE_CASE(3);
     SETK_WPE_CASE(4);
     SETK_WPE_CASE(5);
-    SETK_WPE_CASE(6);
     SETK_WPE_CASE(8);
     SETK_WPE_CASE(10);
     SETK_WPE_CASE(12);
@@ -570,6 +582,12 @@ hipError_t launch_wpe_step_batch(const void* d_tbl, int n_utts, int N, int F, in
     hipLaunchKernelGGL(kern, dim3(F, n_utts), dim3(256), lds, s, static_cast<const WpeArgs*>(d_tbl),
                        wpe_chunk_frames(N, taps));
     return hipGetLastError();
+}
+
+void wpe_form(int N, int taps, int* wide, int* tiles_per_wave, int* chunk_frames) {
+    if (wide) *wide = wpe_is_wide(N, taps) ? 1 : 0;
+    if (tiles_per_wave) *tiles_per_wave = wpe_tiles_per_wave(N, taps);
+    if (chunk_frames) *chunk_frames = wpe_chunk_frames(N, taps);
 }
 
 }  // namespace setk

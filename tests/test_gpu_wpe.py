@@ -125,8 +125,10 @@ def test_wpe_beyond_256_tap_rows_is_refused():
 def test_wpe_wide_shapes_match_the_oracle(N, taps):
     """Channels x taps whose R does not fit the 160 KB of a CU (the reference has no bound,
     libs/wpe.py:58-81): R is factored in global memory, everything else is the LDS form's
-    code.  Against the complex128 oracle on reverberant (AR-filtered) data, two iterations,
-    plus the batch entry with a second, shorter utterance."""
+    code.  (8, 11) is the largest 8-channel shape that still runs the LDS form (NK = 88, 20
+    tiles per wavefront); the wide form starts at 8 x 12 and 16 x 6.  Against the complex128
+    oracle on reverberant (AR-filtered) data, two iterations, plus the batch entry with a
+    second, shorter utterance."""
     from oracle import np_oracle as o
     from setk_amd.libs import wpe as W
     rng = np.random.default_rng(100 * N + taps)
