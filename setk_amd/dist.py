@@ -200,13 +200,6 @@ class Shard:
             return False
         uid = self._star.broadcast(uid, 128)
         comm = ctypes.c_void_p()
-        lib.setk_comm_create.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_char_p,
-                                         ctypes.c_int, ctypes.c_int]
-        lib.setk_comm_allreduce_f64.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double),
-                                                ctypes.c_int, ctypes.c_int]
-        lib.setk_comm_barrier.argtypes = [ctypes.c_void_p]
-        lib.setk_comm_destroy.argtypes = [ctypes.c_void_p]
-        lib.setk_comm_last_error.restype = ctypes.c_char_p
         rc = lib.setk_comm_create(ctypes.byref(comm), self.local_rank, uid, self.rank, self.world)
         good = 1.0 if rc == 0 else 0.0
         if sum(self._star.allreduce([good])) < self.world:

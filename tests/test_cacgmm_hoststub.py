@@ -6,30 +6,16 @@ slabs of the samples, the starts and the masks, growth from a small batch to a l
 hoststub_report, that launches were counted and no copy left its allocation.  The engine runs in
 a child process because SETK_LIB is read at import.
 """
-import os
-import subprocess
-import sys
+from hoststub_case import report, run_child
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOP, F = 256, 257
 
 
 def test_cacgmm_estimator_on_the_plain_stand_in():
-    r = subprocess.run(["bash", os.path.join(ROOT, "tools", "hoststub", "build.sh")], capture_output=True,
-                       text=True, timeout=900, env=dict(os.environ, PLAIN="1"))
-    assert r.returncode == 0, r.stdout + r.stderr
-    env = dict(os.environ, SETK_ALLOW_HOSTSTUB="1", SETK_TORCH_FREE="1", OMP_NUM_THREADS="1",
-               SETK_LIB=os.path.join(ROOT, "_abl", "libsetk_hoststub.so"),
-               PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
-    env.pop("HOSTSTUB_TRACE", None)
-    r = subprocess.run([sys.executable, os.path.abspath(__file__)], capture_output=True, text=True,
-                       timeout=300, env=env, cwd=ROOT)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    assert "cacgmm estimator on the stand-in: ok" in r.stdout, r.stdout[-2000:]
+    run_child(__file__, "cacgmm estimator on the stand-in: ok")
 
 
 def _child():
-    import ctypes
     import numpy as np
     import pytest
     from setk_amd import _ffi
@@ -46,12 +32,6 @@ def _child():
     def frames_of(u):
         C, size = channels_and_size(u)
         return 1 + (size // C) // HOP
-
-    def report():
-        vals = [ctypes.c_long() for _ in range(4)]
-        first = ctypes.create_string_buffer(512)
-        _ffi.load_library().hoststub_report(*[ctypes.byref(v) for v in vals], first, 512)
-        return [v.value for v in vals] + [first.value.decode()]
 
     def starts_of(batch, K):
         return [np.full((K, F, frames_of(u)), 1.0 / K) for u in batch]

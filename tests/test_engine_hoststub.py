@@ -5,30 +5,16 @@ from a small batch to a larger one, output shapes and dtypes, the None / status 
 close() -- and, through hoststub_report, that launches were counted and no copy left its
 allocation.  The engines run in a child process because SETK_LIB is read at import.
 """
-import os
-import subprocess
-import sys
+from hoststub_case import report, run_child
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOP, F = 256, 257
 
 
 def test_engines_on_the_plain_stand_in():
-    r = subprocess.run(["bash", os.path.join(ROOT, "tools", "hoststub", "build.sh")], capture_output=True,
-                       text=True, timeout=900, env=dict(os.environ, PLAIN="1"))
-    assert r.returncode == 0, r.stdout + r.stderr
-    env = dict(os.environ, SETK_ALLOW_HOSTSTUB="1", SETK_TORCH_FREE="1", OMP_NUM_THREADS="1",
-               SETK_LIB=os.path.join(ROOT, "_abl", "libsetk_hoststub.so"),
-               PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
-    env.pop("HOSTSTUB_TRACE", None)
-    r = subprocess.run([sys.executable, os.path.abspath(__file__)], capture_output=True, text=True,
-                       timeout=300, env=env, cwd=ROOT)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    assert "engines on the stand-in: ok" in r.stdout, r.stdout[-2000:]
+    run_child(__file__, "engines on the stand-in: ok")
 
 
 def _child():
-    import ctypes
     import numpy as np
     import pytest
     from setk_amd import _ffi
@@ -49,12 +35,6 @@ def _child():
         N = size // C
         T = 1 + N // HOP
         return C, N, T, HOP * (T - 1)
-
-    def report():
-        vals = [ctypes.c_long() for _ in range(4)]
-        first = ctypes.create_string_buffer(512)
-        _ffi.load_library().hoststub_report(*[ctypes.byref(v) for v in vals], first, 512)
-        return [v.value for v in vals] + [first.value.decode()]
 
     def zeros(a, shape, dtype):
         assert isinstance(a, np.ndarray) and a.shape == shape and a.dtype == dtype, (a.shape, a.dtype, shape, dtype)

@@ -646,13 +646,6 @@ def test_rccl_comm_through_the_c_abi_single_rank():
     import ctypes
     from setk_amd import _ffi
     lib = _ffi.load_library()
-    lib.setk_comm_create.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_char_p,
-                                     ctypes.c_int, ctypes.c_int]
-    lib.setk_comm_allreduce_f64.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), ctypes.c_int,
-                                            ctypes.c_int]
-    lib.setk_comm_barrier.argtypes = [ctypes.c_void_p]
-    lib.setk_comm_destroy.argtypes = [ctypes.c_void_p]
-    lib.setk_comm_last_error.restype = ctypes.c_char_p
     uid = ctypes.create_string_buffer(128)
     assert lib.setk_comm_unique_id(uid) == 0, lib.setk_comm_last_error()
     assert any(uid.raw)

@@ -8,29 +8,18 @@ device memory is held after close.  The engine runs in a child process because S
 import.
 """
 import os
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from hoststub_case import report, run_child
+
 HOP, F = 256, 257
 
 
 def test_ns_engine_and_cli_on_the_plain_stand_in(tmp_path):
-    r = subprocess.run(["bash", os.path.join(ROOT, "tools", "hoststub", "build.sh")], capture_output=True,
-                       text=True, timeout=900, env=dict(os.environ, PLAIN="1"))
-    assert r.returncode == 0, r.stdout + r.stderr
-    env = dict(os.environ, SETK_ALLOW_HOSTSTUB="1", SETK_TORCH_FREE="1", OMP_NUM_THREADS="1",
-               SETK_LIB=os.path.join(ROOT, "_abl", "libsetk_hoststub.so"),
-               PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
-    env.pop("HOSTSTUB_TRACE", None)
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), str(tmp_path)], capture_output=True, text=True,
-                       timeout=300, env=env, cwd=ROOT)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    assert "noise suppression on the stand-in: ok" in r.stdout, r.stdout[-2000:]
+    run_child(__file__, "noise suppression on the stand-in: ok", str(tmp_path))
 
 
 def _child(tmp):
-    import ctypes
     import numpy as np
     import pytest
     import scipy.io.wavfile
@@ -49,12 +38,6 @@ def _child(tmp):
 
     def frames_of(u):
         return 1 + channels_and_size(u)[1] // HOP
-
-    def report():
-        vals = [ctypes.c_long() for _ in range(4)]
-        first = ctypes.create_string_buffer(512)
-        _ffi.load_library().hoststub_report(*[ctypes.byref(v) for v in vals], first, 512)
-        return [v.value for v in vals] + [first.value.decode()]
 
     # two calls per engine, the second larger and ragged, so that every buffer grows once
     small = [f32(4000), pcm(4300)]

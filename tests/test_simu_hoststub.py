@@ -8,25 +8,16 @@ sharding and resume -- and, through hoststub_report, that no copy left its alloc
 memory is held after close.  Runs in a child process because SETK_LIB is read at import.
 """
 import os
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+from hoststub_case import report, run_child  # noqa: E402
+
 
 def test_simu_engine_and_cli_on_the_plain_stand_in(tmp_path):
-    r = subprocess.run(["bash", os.path.join(ROOT, "tools", "hoststub", "build.sh")], capture_output=True,
-                       text=True, timeout=900, env=dict(os.environ, PLAIN="1"))
-    assert r.returncode == 0, r.stdout + r.stderr
-    env = dict(os.environ, SETK_ALLOW_HOSTSTUB="1", SETK_TORCH_FREE="1", OMP_NUM_THREADS="1",
-               SETK_LIB=os.path.join(ROOT, "_abl", "libsetk_hoststub.so"),
-               PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
-    env.pop("HOSTSTUB_TRACE", None)
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), str(tmp_path)], capture_output=True, text=True,
-                       timeout=300, env=env, cwd=ROOT)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    assert "data simulation on the stand-in: ok" in r.stdout, r.stdout[-2000:]
+    run_child(__file__, "data simulation on the stand-in: ok", str(tmp_path))
 
 
 def _child(tmp):
@@ -45,12 +36,6 @@ def _child(tmp):
 
     def f32(*shape):
         return (0.1 * rng.standard_normal(shape)).astype(np.float32)
-
-    def report():
-        vals = [ctypes.c_long() for _ in range(4)]
-        first = ctypes.create_string_buffer(512)
-        _ffi.load_library().hoststub_report(*[ctypes.byref(v) for v in vals], first, 512)
-        return [v.value for v in vals] + [first.value.decode()]
 
     ctx = _ffi.default_context()
     # ---- the operator: validation and limits ----
