@@ -857,6 +857,55 @@ int setk_enhance_batch_taps(setk_handle_t h, const setk_bf_opts* opts, int n_utt
                             const float* const* mask_n, void* const* wave,
                             int* status, const setk_batch_taps* taps, void* stream);
 
+/* ---- block-online beamforming ----------------------------------------------
+ * setk_online_num_chunks: ceil(T / chunk_size) for a signal of num_samples under the plan (T =
+ * setk_stft_num_frames), i.e. the loop count of do_online_beamform
+ * (apply_adaptive_beamformer.py:25-47); negative (SETK_ERR_*) without a plan or for
+ * chunk_size < 1. */
+int setk_online_num_chunks(setk_handle_t h, int num_samples, int chunk_size);
+
+/* setk_enhance_online_batch: OnlineMvdrBeamformer / OnlineGevdBeamformer.run
+ * (libs/beamformer.py:286-320, 685-724) under do_online_beamform
+ * (apply_adaptive_beamformer.py:25-47), then post-mask, inverse_stft and renorm as
+ * setk_enhance_batch, for a batch of utterances that share the channel count; the block-online
+ * form of apply-supervised-mvdr.cc:198-217 (--update-periods).  Chunk c of an utterance covers the
+ * frames [c S, min((c + 1) S, T)), S = chunk_size:
+ *   rs_c, rn_c   compute_covar over the chunk's frames alone (masks mask_s, and mask_n or
+ *                1 - mask_s; denominator max(sum of the chunk's mask, 1e-6))
+ *   Rs_c = alpha Rs_{c-1} + phi_c rs_c, Rn_c likewise, Rs_{-1} = 0
+ *   phi_0 = 1, phi_c = 1 - alpha for c > 0.  (The reference class never clears its `reset`
+ *                member (:296-317), so its phi stays 1; this library follows the stated recursion.)
+ *   w_c          the MVDR / GEV weight of (Rs_c, Rn_c) under the library's gauge; with
+ *                SETK_FLAG_BAN scaled by do_ban(w_c, rn_c) -- the chunk's own UNSMOOTHED rn_c
+ *   frame t      is beamformed with w_{t / S}
+ * No state survives an utterance.  audio, num_samples, mask_s, mask_n, wave, status, stream: as
+ * setk_enhance_batch; status[u] is the worst bin of the utterance's worst chunk.  Taps (every
+ * member may be NULL; device or host memory), chunks utterance by utterance, chunks_total = sum of
+ * setk_online_num_chunks:
+ *   Rs, Rn   [chunks_total][F][C][C] complex64  the smoothed Rs_c, Rn_c
+ *   weight   [chunks_total][F][C]    complex64  w_c (after BAN when requested)
+ * Supported: kinds SETK_BF_MVDR and SETK_BF_GEVD; flags BAN, POST_MASK, CLAMP_MASK, IN_PCM16
+ * (an even hop), OUT_PCM16, NO_RENORM, NO_GAUGE; 1 <= C <= 8; the n_fft = 512 plan -- anything
+ * else is SETK_ERR_UNSUPPORTED.  SETK_ERR_INVALID: chunk_size < 1, alpha outside [0, 1), null
+ * pointers.  Scratch (the slabs and planes of every chunk) comes from the handle's arena; the call
+ * returns when the work has run.  With setk_set_profiling the stage times of setk_last_stage_ms
+ * are out[0] STFT + chunk covariances, out[1] smoothing + weights + BAN, out[2] beamform + iSTFT,
+ * out[3] renorm. */
+typedef struct setk_online_opts {
+    int chunk_size;
+    float alpha;
+} setk_online_opts;
+typedef struct setk_online_taps {
+    float* Rs;
+    float* Rn;
+    float* weight;
+} setk_online_taps;
+int setk_enhance_online_batch(setk_handle_t h, const setk_bf_opts* opts, const setk_online_opts* online,
+                              int n_utts, int num_channels, const float* const* audio,
+                              const int* num_samples, const float* const* mask_s,
+                              const float* const* mask_n, void* const* wave, int* status,
+                              const setk_online_taps* taps, void* stream);
+
 /* ---- multi-GPU: the work-queue barrier on RCCL ------------------------------
  * The path shards by utterance with no data exchange (the reference: split_scp.pl + run.pl
  * JOB=1:nj, scripts/run_adapt_beamformer.sh:69-92).  One process per GPU needs a start / finish

@@ -388,9 +388,20 @@ class BatchTaps(ctypes.Structure):
     _fields_ = [("Rs", c_void_p), ("Rn", c_void_p), ("weight", c_void_p), ("maxabs", c_void_p)]
 
 
+class OnlineOpts(ctypes.Structure):
+    _fields_ = [("chunk_size", c_int), ("alpha", c_float)]
+
+
+class OnlineTaps(ctypes.Structure):
+    _fields_ = [("Rs", c_void_p), ("Rn", c_void_p), ("weight", c_void_p)]
+
+
 PROTOTYPES.update(
     setk_enhance_batch=(I, [H, POINTER(BfOpts), I, I, PP, IP, PP, PP, PP, IP, S]),
     setk_enhance_batch_taps=(I, [H, POINTER(BfOpts), I, I, PP, IP, PP, PP, PP, IP, POINTER(BatchTaps), S]),
+    setk_online_num_chunks=(I, [H, I, I]),
+    setk_enhance_online_batch=(I, [H, POINTER(BfOpts), POINTER(OnlineOpts), I, I, PP, IP, PP, PP, PP, IP,
+                                   POINTER(OnlineTaps), S]),
     setk_comm_unique_id=(I, [c_char_p]),
     setk_comm_create=(I, [POINTER(H), I, c_char_p, I, I]),
     setk_comm_allreduce_f64=(I, [H, POINTER(c_double), I, I]),
@@ -981,6 +992,27 @@ class Context:
         else:
             self._run("setk_enhance_batch", *args, stream=stream)
         return list(ST) if want_status else None
+
+    # -- block-online beamforming -------------------------------------------------
+    def online_num_chunks(self, num_samples, chunk_size):
+        """ceil(T / chunk_size) under the plan: the chunks of one utterance."""
+        n = self._lib.setk_online_num_chunks(self._h, int(num_samples), int(chunk_size))
+        if n < 0:
+            self.check(n)
+        return n
+
+    def enhance_online_batch(self, opts, chunk_size, alpha, num_channels, audio_ptrs, num_samples, mask_ptrs,
+                             itf_ptrs, wave_ptrs, status=None, taps=None, stream=None):
+        """setk_enhance_online_batch.  status: int32[n] (numpy or a device address) or None; taps:
+        dict with any of Rs, Rn ([chunks_total][F][C][C] complex64) and weight ([chunks_total][F][C]
+        complex64), numpy arrays or device addresses."""
+        n = len(audio_ptrs)
+        online = OnlineOpts(int(chunk_size), float(alpha))
+        tp = OnlineTaps(*[_ptr(taps.get(k)) for k in ("Rs", "Rn", "weight")]) if taps else None
+        st = None if status is None else ctypes.cast(c_void_p(_ptr(status)), POINTER(c_int))
+        self._run("setk_enhance_online_batch", ctypes.byref(opts), ctypes.byref(online), n, int(num_channels),
+                  _ptrs(audio_ptrs), _ints(num_samples, n), _ptrs(mask_ptrs, n), _ptrs(itf_ptrs, n),
+                  _ptrs(wave_ptrs, n), st, ctypes.byref(tp) if tp else None, stream=stream)
 
     # -- stage timings ------------------------------------------------------------
     def set_profiling(self, on):

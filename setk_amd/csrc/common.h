@@ -133,6 +133,22 @@ struct Pass2Args {
     const float* mc_win;     // [8][64] analysis window rows x 2^10 / peak
     const float* mc_syn;     // [8][64] synthesis window rows x peak / 2^10 / 512 / sum(window^2)
     const float* mc_edge;    // [8][64] corrections of the single-contribution blocks (first | last)
+    // block-online beamforming (launch_pass2_online): frame t of utterance u takes weight set
+    // chunk0[u] + t / chunk_size of `weight` ([chunks_total][C][kBinsPad] float2)
+    const int* chunk0;       // [n_utts]
+    int chunk_size;
+};
+
+// block-online beamforming (online.hip): chunk k of the batch (utterance u owns chunks
+// [chunk0[u], chunk0[u + 1])) is a virtual utterance of the weight solve
+struct OnlineArgs {
+    const float* partials;    // pass 1's slabs, each over frames of one chunk
+    const int2* chunk_parts;  // [chunks_total] (first slab, slabs)
+    const int* chunk0;        // [n_utts + 1]
+    float* covar;             // [chunks_total][4 NP][kBinsPad]: the smoothed Rs_c | Rn_c
+    float* rn_chunk;          // [chunks_total][2 NP][kBinsPad]: the chunk's own rn_c (BAN), or null
+    int num_channels;
+    float alpha;              // R_c = alpha R_{c-1} + phi_c r_c; phi_0 = 1, phi_c = 1 - alpha
 };
 
 struct ScaleArgs {
@@ -156,7 +172,12 @@ hipError_t launch_finalize(const FinalizeArgs& a, int n_utts, hipStream_t s);
 hipError_t launch_solve(const SolveArgs& a, hipStream_t s);
 hipError_t launch_pmwf_select(const SolveArgs& a, int* ref_out, hipStream_t s);
 hipError_t launch_pass2(int C, bool istft_only, const Pass2Args& a, int n_items, hipStream_t s);
+hipError_t launch_pass2_online(int C, const Pass2Args& a, int n_items, hipStream_t s, bool pcm16);
 hipError_t launch_scale(const ScaleArgs& a, int n_utts, int max_len, hipStream_t s);
+hipError_t launch_online_smooth(const OnlineArgs& a, int n_utts, hipStream_t s);
+hipError_t launch_online_ban(int C, float* weight, const float* rn_chunk, int n_chunks, hipStream_t s);
+hipError_t launch_online_status(const int* chunk_status, const int* chunk0, int n_utts, int* status,
+                                hipStream_t s);
 size_t pass2_lds_bytes(int C, int keep);
 
 // modular helpers

@@ -17,6 +17,7 @@
 #include "fft512.h"
 #include <cstdio>
 #include <cstdlib>
+#include <type_traits>
 
 namespace setk {
 
@@ -47,7 +48,13 @@ size_t pass2_lds_bytes(int C, int keep) {
 // its lanes' accumulators (lane la owns bins k = la + 16 m and 256 - k), merges,
 // inverse-transforms and leaves the windowed frame in its LDS slot.  Nothing in
 // that chain needs a workgroup barrier; only the overlap-add does.
-template <int C, bool ISTFT_ONLY>
+//
+// ONLINE (block-online beamforming, online.hip; 1: float32 samples, 2: 16-bit PCM): the weight
+// set is chosen per FRAME -- frame t takes set chunk0[utt] + t / chunk_size of a.weight, read
+// from global memory by the quad-row that owns the frame (an item that begins at a chunk
+// boundary still transforms the frames before it for the overlap-add, and those belong to the
+// previous chunk).  ONLINE == 0 compiles to what it was.
+template <int C, bool ISTFT_ONLY, int ONLINE = 0>
 __global__ __launch_bounds__(kPass2Threads, kPass2WavesPerSimd) void beamform_istft_kernel(Pass2Args a) {
     constexpr int NT = kPass2Threads;
     constexpr int F = kBins;
@@ -84,7 +91,7 @@ __global__ __launch_bounds__(kPass2Threads, kPass2WavesPerSimd) void beamform_is
     const cf* win_row = win_l + la * LaneTab<kRow2>::lstride;
     const cf* tw_row = tw_l + la * LaneTab<kRow2>::lstride;
     const cf* tw5_row = tw5_l + la * LaneTab<kRow2>::lstride5;
-    if (!ISTFT_ONLY) {
+    if (!ISTFT_ONLY && ONLINE == 0) {
         const cf* wsrc = reinterpret_cast<const cf*>(a.weight) + (size_t)wi.utt * C * kBinsPad;
         for (int i = tid; i < C * F; i += NT) {
             const int c = i / F, f = i - c * F;
@@ -124,21 +131,36 @@ __global__ __launch_bounds__(kPass2Threads, kPass2WavesPerSimd) void beamform_is
                 }
             }
         } else {
-            cf nxt[16];
-            load_raw<const float*>(nxt, ud.audio, n_samp, t * hop - a.g.pad, la, tvalid);
+            typename std::conditional<ONLINE == 2, int, cf>::type nxt[16];  // PCM: packed pairs of samples
+            const cf* wfr = nullptr;  // ONLINE: the weight set of this quad-row's frame
+            if constexpr (ONLINE != 0)
+                wfr = reinterpret_cast<const cf*>(a.weight) +
+                      (size_t)(a.chunk0[wi.utt] + min(t, T - 1) / a.chunk_size) * C * kBinsPad;
+            gcshort_p pcm = (gcshort_p)gptr(ud.audio);  // ONLINE == 2: the next channel to request
+            auto fetch = [&](int c) {
+                if constexpr (ONLINE == 2) {
+                    load_raw_pcm(nxt, pcm, n_samp, t * hop - a.g.pad, la, tvalid);
+                    pcm += ud.ch_stride;
+                } else {
+                    load_raw<const float*>(nxt, ud.audio + (size_t)c * n_samp, n_samp, t * hop - a.g.pad, la,
+                                           tvalid);
+                }
+            };
+            fetch(0);
 #pragma unroll 1
             for (int c = 0; c < C; ++c) {
                 cf v[16];
 #pragma unroll
-                for (int j = 0; j < 16; ++j) v[j] = nxt[j];
+                for (int j = 0; j < 16; ++j) {
+                    if constexpr (ONLINE == 2) v[j] = unpack_pcm(nxt[j]);  // integers as floats: x 2^15, undone below
+                    else v[j] = nxt[j];
+                }
                 apply_window<kRow2>(v, win_row);
-                if (c + 1 < C)
-                    load_raw<const float*>(nxt, ud.audio + (size_t)(c + 1) * n_samp, n_samp, t * hop - a.g.pad,
-                             la, tvalid);
+                if (c + 1 < C) fetch(c + 1);
                 fft256_stage_a_pad<-1, kRow2>(v, slot, tw_row, la);
                 __builtin_amdgcn_wave_barrier();
                 fft256_stage_b_pad<-1, kRow2>(v, slot, la);  // v[pos(kb)] = Z[la + 16 kb]
-                const cf* wc = wtab + c * F;
+                const cf* wc = ONLINE != 0 ? wfr + c * kBinsPad : wtab + c * F;
                 // bins k = la + 16 m and 256 - k: one base register each + immediates
                 const cf* wlo = wc + la;
                 const cf* wmir = wc + (256 - 16 * 7) - la;
@@ -180,6 +202,16 @@ __global__ __launch_bounds__(kPass2Threads, kPass2WavesPerSimd) void beamform_is
                     }
                 }
                 __builtin_amdgcn_wave_barrier();
+            }
+            if constexpr (ONLINE == 2) {
+                // The transform and the products are linear and a power of two scales every
+                // float32 operation exactly: 2^-15 here gives the bits of the float32 form of the
+                // same file (int16 / 32768), at 16 multiplications per frame instead of 32 per channel
+#pragma unroll
+                for (int m = 0; m < 8; ++m) {
+                    Yk[m] = cscale(Yk[m], 3.0517578125e-05f);
+                    Ym[m] = cscale(Ym[m], 3.0517578125e-05f);
+                }
             }
         }
         // ---- optional post-mask, merge into the packed inverse input (registers) ----
@@ -292,10 +324,10 @@ __global__ __launch_bounds__(kPass2Threads, kPass2WavesPerSimd) void beamform_is
     }
 }
 
-template <int C, bool IO>
+template <int C, bool IO, int ONLINE = 0>
 static hipError_t launch_pass2_t(const Pass2Args& a, int n_items, hipStream_t s) {
     const size_t lds = pass2_lds_bytes(IO ? 1 : C, a.g.keep);
-    auto k = beamform_istft_kernel<C, IO>;
+    auto k = beamform_istft_kernel<C, IO, ONLINE>;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
@@ -320,6 +352,26 @@ hipError_t launch_pass2(int C, bool istft_only, const Pass2Args& a, int n_items,
         case 7: return launch_pass2_t<7, false>(a, n_items, s);
         case 8: return launch_pass2_t<8, false>(a, n_items, s);
     }
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_pass2_online(int C, const Pass2Args& a, int n_items, hipStream_t s, bool pcm16) {
+    if (!a.chunk0 || a.chunk_size < 1) return hipErrorInvalidValue;
+#define SETK_CASE(c)                                                   \
+    case c:                                                            \
+        if (pcm16) return launch_pass2_t<c, false, 2>(a, n_items, s);  \
+        return launch_pass2_t<c, false, 1>(a, n_items, s);
+    switch (C) {
+        SETK_CASE(1)
+        SETK_CASE(2)
+        SETK_CASE(3)
+        SETK_CASE(4)
+        SETK_CASE(5)
+        SETK_CASE(6)
+        SETK_CASE(7)
+        SETK_CASE(8)
+    }
+#undef SETK_CASE
     return hipErrorInvalidValue;
 }
 

@@ -16,3 +16,4 @@ from .directional import BatchDirectionalFeatures  # noqa: F401
 from .spatial import BatchSpatialFeatures  # noqa: F401
 from .ns import BatchNoiseSuppressor  # noqa: F401
 from .simu import BatchSimulator  # noqa: F401
+from .online import BatchOnlineEnhancer  # noqa: F401

@@ -26,14 +26,15 @@ import numpy as np
 
 from setk_amd import _ffi
 from setk_amd.dist import Shard
-from setk_amd.engine import BatchEnhancer, Pcm16Frames, compute_vad_masks
+from setk_amd.engine import BatchEnhancer, BatchOnlineEnhancer, Pcm16Frames, compute_vad_masks
 from setk_amd.libs import wavio
 from setk_amd.libs.beamformer import OnlineGevdBeamformer, OnlineMvdrBeamformer
 from setk_amd.libs.data_handler import (NumpyReader, ScriptReader, SpectrogramReader,
                                         WaveReader, WaveWriter)
 from setk_amd.libs.opts import StftParser, strtobool
 from setk_amd.libs.utils import get_logger, inverse_stft, nextpow2
-from setk_amd.sptk._common import complete_wav as _complete_wav, deal, finish, run_batches, stft_kwargs
+from setk_amd.sptk._common import (complete_wav as _complete_wav, deal, finish, run_batches, set_torch_free,
+                                   stft_kwargs)
 
 logger = get_logger(__name__)
 beamformers = ["mvdr", "mpdr", "mpdr-whiten", "gevd", "pmwf-0", "pmwf-1"]
@@ -172,7 +173,75 @@ def _wav_done(args):
     return lambda key: _complete_wav(os.path.join(args.dst_dir, f"{key}.wav"))
 
 
+def _online_on_device(args):
+    """The batched device engine (BatchOnlineEnhancer) runs the block-online mode of the fused
+    kernels' geometry: the 512-point transform, up to 8 channels, no VAD filtering (its threshold
+    is a host-side sort over |X_0|).  Everything else keeps the per-utterance loop."""
+    n_fft = nextpow2(args.frame_len) if args.round_power_of_two else args.frame_len
+    return n_fft == 512 and not 0.5 < args.vad_proportion < 1 and 1 <= args.channels <= 8 and \
+        args.beamformer in ("mvdr", "gevd")
+
+
+def run_online_batched(args, shard):
+    """--online.chunk-size through BatchOnlineEnhancer: batches of --batch-utts utterances, the
+    log lines and the LinAlgError skip of the per-utterance loop."""
+    wav_reader = WaveReader(args.wav_scp, sr=args.sr)
+    MaskReader = {"numpy": NumpyReader, "kaldi": ScriptReader}[args.fmt]
+    tgt = MaskReader(args.tgt_mask)
+    itf = MaskReader(args.itf_mask) if args.itf_mask else None
+    set_torch_free(args, shard)
+    device = None if args.device < 0 else args.device
+    if device is None and shard.world > 1:
+        device = shard.device
+    engine = BatchOnlineEnhancer(beamformer=args.beamformer, chunk_size=args.chunk_size, alpha=args.alpha,
+                                 ban=bool(args.ban), post_mask=bool(args.mask), pcm16=True, device=device,
+                                 **stft_kwargs(args))
+    logger.info(f"Using online {args.beamformer} beamformer, chunk size = {args.chunk_size:d}")
+    keys = deal(args, shard, wav_reader, _wav_done(args))
+
+    def utterances():
+        for key in keys:
+            if key not in tgt:
+                continue
+            pcm = wav_reader.read_pcm16(key) if args.device_ingest else None
+            if pcm is not None:
+                ch0 = pcm[:, 0].astype(np.float32) / np.float32(32768.0)
+                samps, channels = Pcm16Frames(pcm), pcm.shape[1]
+            else:
+                samps = wav_reader.read(key)
+                if samps.ndim == 1:
+                    samps = samps[None]
+                ch0, channels = samps[0], samps.shape[0]
+            if channels != args.channels:
+                raise ValueError(f"utterance {key} has {channels} channels, --online.channels says "
+                                 f"{args.channels}")
+            power = np.linalg.norm(ch0, 2)**2 / ch0.size
+            logger.info(f"Processing utterance {key}, " +
+                        f"signal power {10 * np.log10(power + 1e-5):.2f}...")
+            yield key, samps, tgt[key], None if itf is None else itf[key]
+
+    with WaveWriter(args.dst_dir, sr=args.sr) as writer:
+        def flush(pending):
+            done = 0
+            results = engine.enhance([(s, m, i) for (_, s, m, i) in pending])
+            for (key, _, _, _), (pcm, status) in zip(pending, results):
+                if status != 0:
+                    logger.error(f"Raise linalg error: {key}")
+                    continue
+                writer.write_pcm16(key, pcm)
+                done += 1
+            return done
+
+        try:
+            num_done = run_batches(utterances(), args.batch_utts, flush)
+        finally:
+            engine.close()
+    return num_done, len(wav_reader)
+
+
 def run_online(args, shard):
+    if _online_on_device(args):
+        return run_online_batched(args, shard)
     stft_kwargs = dict(frame_len=args.frame_len, frame_hop=args.frame_hop, window=args.window,
                        center=args.center, transpose=False)
     reader = SpectrogramReader(args.wav_scp, round_power_of_two=args.round_power_of_two,
