@@ -103,8 +103,8 @@ extern "C" {
  * streaming kernels then read 2 bytes per sample and scale by 2^-15 inside their transforms
  * (folded into the window tables: a power of two, so the results are bit for bit those of the
  * float32 call on pcm / 32768, i.e. on read_wav's dtype="float32" samples, libs/utils.py:80-90).
- * Needs hop = n_fft / 2 (the CLI default 512 / 256); otherwise SETK_ERR_UNSUPPORTED -- convert
- * with setk_pcm16_to_float_batch. */
+ * Needs hop = n_fft / 2 (the CLI default 512 / 256) and at most 8 channels; otherwise
+ * SETK_ERR_UNSUPPORTED -- convert with setk_pcm16_to_float_batch. */
 #define SETK_FLAG_IN_PCM16 0x80
 
 typedef struct setk_context* setk_handle_t;
@@ -806,7 +806,7 @@ int setk_simu_batch(setk_handle_t h, int n_mix, const setk_simu_recipe* recipes,
 /* ---- fused hot path ------------------------------------------------------
  * The compute body of apply_adaptive_beamformer.py:130-178 for a batch of
  * utterances that share the channel count, in four kernel stages:
- *   1. windowed rFFT + masked outer-product accumulation (never stores X)
+ *   1. windowed rFFT + masked outer-product accumulation (never stores X; C > 8: below)
  *   2. batched per-bin weight solve
  *   3. rFFT recompute + w^H x + irFFT + overlap-add
  *   4. max-abs renorm (to max|input|) and emit float32 (or PCM16)
@@ -829,7 +829,26 @@ int setk_simu_batch(setk_handle_t h, int n_mix, const setk_simu_recipe* recipes,
  * status[u]  int, SETK_NUM_* (worst bin of the utterance); host memory (the call
  *            then synchronises the stream), device memory (asynchronous) or NULL
  * The pointer tables and num_samples are HOST arrays of n_utts entries.
- * Requires the n_fft = 512 plan and 1 <= C <= 8. */
+ * Requires the n_fft = 512 plan and 1 <= C <= 16 (otherwise SETK_ERR_UNSUPPORTED).
+ *
+ * 9 <= C <= 16 (the wide path, csrc/wide.hip): the same four stages and the same results, every
+ * kind, BAN, post mask, interferer mask, status, taps, either output type, any stream; but X IS
+ * stored once -- stage 1 writes the spectra bin-major, X[f][c][t] complex64 with the frames
+ * contiguous at pitch Tp = (T + 3) & ~3, and accumulates the covariances from them on the fp32
+ * matrix cores (one 32 x 32 real tile per covariance and bin, slabs of 128 frames summed in
+ * order: a result does not depend on what else is in the batch); stage 2 solves the problems
+ * embedded in 16 x 16 ones (blkdiag(Rs, 0), blkdiag(Rn, max diag(Rn) I)); stage 3 beamforms from
+ * the stored spectra and inverts.  SETK_FLAG_IN_PCM16 is refused there with
+ * SETK_ERR_UNSUPPORTED: convert with setk_pcm16_to_float_batch.  Scratch from the handle's
+ * arena, per utterance (F = 257):
+ *     8 F C Tp                    the spectra
+ *   + 8 F T                       the beamformed spectrogram
+ *   + 4 F 824 ceil(T / 128)       the covariance slabs
+ *   + 4 264 (4 x 136 + 2 x 16)    planes and weights (6 x 136 planes for MPDR; PMWF with the
+ *                                 SNR-selected reference: + F 16 (16 + 256 x 8) bytes)
+ *   + 4 L_u                       the float32 wave, with SETK_FLAG_OUT_PCM16 only
+ * -- about 21 MB for 16 channels x 10 s.  When the arena cannot provide it the call returns
+ * SETK_ERR_NOMEM and has launched nothing. */
 int setk_enhance_batch(setk_handle_t h, const setk_bf_opts* opts, int n_utts,
                        int num_channels, const float* const* audio,
                        const int* num_samples, const float* const* mask_s,
@@ -844,7 +863,9 @@ int setk_enhance_batch(setk_handle_t h, const setk_bf_opts* opts, int n_utts,
  *            STFT+covariance kernel and its reduction (libs/beamformer.py:87-103)
  *   weight   [n_utts][F][C]    complex64  beamformer weights (libs/beamformer.py
  *            weight() of the selected class, after BAN when requested)
- *   maxabs   [n_utts] float32  max |audio| (WaveReader.maxabs, the renorm target) */
+ *   maxabs   [n_utts] float32  max |audio| (WaveReader.maxabs, the renorm target)
+ * With 9 <= C <= 16 the taps are the C x C matrices and C weights as well (the padding of the
+ * 16 x 16 embedding is not shown), Hermitian bit for bit. */
 typedef struct setk_batch_taps {
     float* Rs;
     float* Rn;

@@ -5,6 +5,155 @@
 
 using namespace setk;
 
+namespace {
+
+// setk_enhance_batch(_taps) for 9 to 16 channels (wide.hip): the spectra make one round trip
+// through the arena in the bin-major layout -- STFT, covariances on the fp32 matrix cores,
+// their reduction into the solve's 16-lane planes, the solve as it is, the beamformer on the
+// spectra, the iSTFT-only pass 2, renorm.  Arguments and options have been checked.
+int enhance_wide(setk_handle_t h, const setk_bf_opts* opts, int n_utts, int C, const float* const* audio,
+                 const int* num_samples, const float* const* mask_s, const float* const* mask_n,
+                 void* const* wave, int* status, const setk_batch_taps* taps, hipStream_t s) {
+    const int kind = opts->kind;
+    const bool mpdr = (kind == SETK_BF_MPDR || kind == SETK_BF_MPDR_WHITEN);
+    const bool pcm16 = (opts->flags & SETK_FLAG_OUT_PCM16) != 0;
+    constexpr int Cp = kMaxChannels16, NP = npairs(kMaxChannels16);
+    const int planes_out = mpdr ? 6 * NP : 4 * NP;
+
+    // ---- descriptors and work lists: [0] STFT, covariance, beamformer; [1] iSTFT ----
+    std::vector<UttDesc> uds = zeroed_utts(n_utts), yds = zeroed_utts(n_utts);
+    std::vector<WorkItem> items_stft, items_cov, items_istft;
+    int max_len = 0, max_samples = 0, max_frames = 0, nparts_total = 0;
+    for (int u = 0; u < n_utts; ++u) {
+        UttDesc& ud = uds[u];
+        if (!audio[u] || !mask_s[u] || !wave[u] || (mask_n && !mask_n[u]))
+            return fail(h, SETK_ERR_INVALID, "null utterance pointer");
+        const int T = setk_stft_num_frames(h, num_samples[u]);
+        if (T < 0) return T;
+        ud.audio = audio[u];
+        ud.mask_s = mask_s[u];
+        ud.mask_n = mask_n ? mask_n[u] : nullptr;
+        ud.num_samples = num_samples[u];
+        ud.num_frames = T;
+        ud.out_len = setk_istft_num_samples(h, T, -1);
+        ud.part0 = nparts_total;
+        ud.nparts = push_items(&items_cov, u, T, kWideSlab, kWideSlab, &nparts_total);
+        push_items(&items_stft, u, T, 64, 64);
+        push_items(&items_istft, u, T, 128, kSuperTile);
+        max_len = std::max(max_len, ud.out_len);
+        max_samples = std::max(max_samples, ud.num_samples);
+        max_frames = std::max(max_frames, T);
+        yds[u].mask_s = ud.mask_s;
+        yds[u].num_frames = T;
+        yds[u].out_len = ud.out_len;
+        yds[u].wave_out = wave[u];
+    }
+
+    // ---- scratch: everything is taken before anything is launched ----
+    SETK_TRY(carve_wave_f32(h, yds, wave, pcm16));
+    for (int u = 0; u < n_utts; ++u) {
+        const size_t T = (size_t)uds[u].num_frames, Tp = (T + 3) & ~(size_t)3;
+        float *xb, *y;
+        SETK_TRY(arena_get(h, std::max<size_t>((size_t)kBins * C * Tp * sizeof(float2), 256), &xb));
+        SETK_TRY(arena_get(h, std::max<size_t>(T * kBins * sizeof(float2), 256), &y));
+        uds[u].wave_out = xb;
+        uds[u].wave_f32 = y;
+        yds[u].audio = y;  // ISTFT mode: per-item spectrogram
+    }
+    float *d_part, *d_covar, *d_w;
+    unsigned* d_small;
+    SETK_TRY(arena_get(h, std::max<size_t>((size_t)nparts_total * kBins * kWidePartFloats * 4, 256), &d_part));
+    SETK_TRY(arena_get(h, (size_t)n_utts * planes_out * kBinsPad * 4, &d_covar));
+    SETK_TRY(arena_get(h, (size_t)n_utts * Cp * kBinsPad * 8, &d_w));
+    SETK_TRY(arena_get(h, (size_t)n_utts * 3 * 4, &d_small));
+    unsigned* d_norm = d_small;
+    unsigned* d_omax = d_small + n_utts;
+    int* d_status = reinterpret_cast<int*>(d_small + 2 * n_utts);
+    SolveArgs sa;
+    memset(&sa, 0, sizeof(sa));
+    const bool snr_ref = kind == SETK_BF_PMWF && opts->pmwf_ref < 0;
+    if (snr_ref) {
+        SETK_TRY(arena_get(h, (size_t)n_utts * kBins * Cp * 2 * sizeof(double), &sa.snr_acc));
+        SETK_TRY(arena_get(h, (size_t)n_utts * kBins * Cp * Cp * 8, &sa.wmat));
+    }
+    OutBuf tap_rs, tap_rn, tap_w;
+    if (taps && taps->Rs) SETK_TRY(stage_out(h, taps->Rs, (size_t)n_utts * kBins * C * C * sizeof(float2), &tap_rs));
+    if (taps && taps->Rn) SETK_TRY(stage_out(h, taps->Rn, (size_t)n_utts * kBins * C * C * sizeof(float2), &tap_rn));
+    if (taps && taps->weight) SETK_TRY(stage_out(h, taps->weight, (size_t)n_utts * kBins * C * sizeof(float2), &tap_w));
+    DescTables t_stft, t_istft;
+    const WorkItem* d_items_cov;
+    SETK_TRY(upload_tables(h, uds, items_stft, s, &t_stft));
+    SETK_TRY(upload(h, items_cov, s, &d_items_cov));
+    SETK_TRY(upload_tables(h, yds, items_istft, s, &t_istft));
+    HIP_TRY(h, hipMemsetAsync(d_small, 0, (size_t)n_utts * 3 * 4, s));
+
+    SETK_TRY(profile_begin(h, s));
+
+    // ---- stage 1: STFT into the bin-major layout, max |audio|, covariances ----
+    Pass1Args p1 = pass1_args(h, t_stft.utts, t_stft.items);
+    HIP_TRY(h, launch_stft_binmajor(C, p1, t_stft.n_items, s));
+    HIP_TRY(h, launch_maxabs(t_stft.utts, C, d_norm, n_utts, max_samples, s));
+    WideArgs wa;
+    memset(&wa, 0, sizeof(wa));
+    wa.utts = t_stft.utts;
+    wa.items = d_items_cov;
+    wa.partials = d_part;
+    wa.covar = d_covar;
+    wa.weight = d_w;
+    wa.num_channels = C;
+    wa.with_ry = mpdr ? 1 : 0;
+    wa.flags = opts->flags;
+    HIP_TRY(h, launch_covar_wide(wa, (int)items_cov.size(), s));
+    HIP_TRY(h, launch_wide_finalize(wa, n_utts, s));
+    SETK_TRY(profile_mark(h, 1, s));
+    if (tap_rs.dev) {
+        HIP_TRY(h, launch_wide_unpack_covar(d_covar, n_utts, planes_out, 0, C, static_cast<float*>(tap_rs.dev), s));
+        SETK_TRY(copy_back(h, tap_rs, s));
+    }
+    if (tap_rn.dev) {
+        HIP_TRY(h, launch_wide_unpack_covar(d_covar, n_utts, planes_out, 2 * NP, C, static_cast<float*>(tap_rn.dev), s));
+        SETK_TRY(copy_back(h, tap_rn, s));
+    }
+
+    // ---- stage 2: weights, the 16-lane form on the padded problems ----
+    sa.covar = d_covar;
+    sa.weight = d_w;
+    sa.status = d_status;
+    sa.n_utts = n_utts;
+    sa.num_bins = kBins;
+    sa.num_channels = Cp;
+    sa.planes = planes_out;
+    sa.kind = kind;
+    sa.flags = opts->flags;
+    sa.rank1 = opts->rank1;
+    sa.pmwf_ref = opts->pmwf_ref;
+    sa.pmwf_beta = opts->pmwf_beta;
+    sa.num_scale = 1.f;
+    HIP_TRY(h, launch_solve(sa, s));
+    if (snr_ref) HIP_TRY(h, launch_pmwf_select(sa, nullptr, s));
+    SETK_TRY(profile_mark(h, 2, s));
+    if (tap_w.dev) {
+        HIP_TRY(h, launch_wide_unpack_weight(d_w, n_utts, C, static_cast<float*>(tap_w.dev), s));
+        SETK_TRY(copy_back(h, tap_w, s));
+    }
+
+    // ---- stage 3: beamform on the spectra, inverse STFT ----
+    HIP_TRY(h, launch_beamform_binmajor(wa, n_utts, max_frames, s));
+    HIP_TRY(h, launch_pass2(1, true, pass2_args(h, t_istft.utts, t_istft.items, d_omax), t_istft.n_items, s));
+    SETK_TRY(profile_mark(h, 3, s));
+
+    // ---- stage 4: renorm ----
+    HIP_TRY(h, launch_scale(scale_args(t_istft.utts, d_norm, d_omax, pcm16), n_utts, max_len, s));
+    SETK_TRY(profile_mark(h, 4, s));
+    bool sync_owed = true;  // the descriptors live in the arena: the call drains
+    if (taps && taps->maxabs) SETK_TRY(copy_out(h, taps->maxabs, d_norm, (size_t)n_utts * 4, s, &sync_owed));
+    if (status) SETK_TRY(copy_out(h, status, d_status, (size_t)n_utts * 4, s, &sync_owed));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    return SETK_OK;
+}
+
+}  // namespace
+
 extern "C" {
 
 int setk_apply_weights_batch(setk_handle_t h, int n_utts, int num_channels,
@@ -90,17 +239,23 @@ int setk_enhance_batch_taps(setk_handle_t h, const setk_bf_opts* opts, int n_utt
         return fail(h, SETK_ERR_INVALID, "bad args");
     SETK_TRY(require_plan512(h));
     const int C = num_channels;
-    if (C < 1 || C > kMaxChannels) return fail(h, SETK_ERR_UNSUPPORTED, "1 <= num_channels <= 8");
+    if (C < 1 || C > kMaxChannels16) return fail(h, SETK_ERR_UNSUPPORTED, "1 <= num_channels <= 16");
     const int kind = opts->kind;
     const bool mpdr = (kind == SETK_BF_MPDR || kind == SETK_BF_MPDR_WHITEN);
     SETK_TRY(check_bf_opts(h, *opts, C, SETK_ERR_UNSUPPORTED,
                            (mpdr && mask_n) ? "fused MPDR derives Ry from mask_s + (1 - mask_s); use the modular API "
                                               "with an interferer mask"
                                             : nullptr));
+    const bool in_pcm = (opts->flags & SETK_FLAG_IN_PCM16) != 0;
+    if (in_pcm && C > kMaxChannels)
+        return fail(h, SETK_ERR_UNSUPPORTED,
+                    "16-bit PCM input (SETK_FLAG_IN_PCM16) is taken for up to 8 channels; convert with "
+                    "setk_pcm16_to_float_batch");
     hipStream_t s;
     SETK_TRY(begin_call(h, stream, &s));
+    if (C > kMaxChannels)
+        return enhance_wide(h, opts, n_utts, C, audio, num_samples, mask_s, mask_n, wave, status, taps, s);
     const bool pcm16 = (opts->flags & SETK_FLAG_OUT_PCM16) != 0;
-    const bool in_pcm = (opts->flags & SETK_FLAG_IN_PCM16) != 0;
     const int NP = npairs(C);
     const StftGeom g = geom_of(h);
 

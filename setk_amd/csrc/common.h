@@ -159,6 +159,32 @@ struct ScaleArgs {
     int pcm16;
 };
 
+// 9 to 16 channels (wide.hip): covariance and beamformer on the bin-major spectra.  The
+// utterance table is read as: audio (the samples), wave_out = the spectra X[f][c][t] that
+// stft_binmajor_kernel writes, wave_f32 = the beamformed [T][F] spectrogram (complex64),
+// mask_s / mask_n, num_frames, part0 / nparts (slabs of kWideSlab frames).
+constexpr int kWideSlab = 128;    // frames per covariance slab: a constant, so that the order of
+                                  // the sums depends on the utterance alone (a multiple of 8)
+// floats of one (slab, bin): three tiles [re 136 | im 136] (speech, noise, all-ones) in the pair
+// order of the 16 x 16 embedding, then sum_t m_s, sum_t m_n (padded to 32 bytes)
+constexpr int kWidePartFloats = 3 * 2 * npairs(kMaxChannels16) + 8;
+struct WideArgs {
+    const UttDesc* utts;
+    const WorkItem* items;  // covariance: one per slab
+    float* partials;        // [nparts_total][kBins][kWidePartFloats]
+    float* covar;           // [n_utts][4 * 136 (+ 2 * 136 when with_ry)][kBinsPad]
+    const float* weight;    // [n_utts][16][kBinsPad] float2
+    int num_channels;       // 9 .. 16
+    int with_ry;            // also the unmasked covariance (MPDR)
+    int flags;
+};
+hipError_t launch_covar_wide(const WideArgs& a, int n_items, hipStream_t s);
+hipError_t launch_wide_finalize(const WideArgs& a, int n_utts, hipStream_t s);
+hipError_t launch_beamform_binmajor(const WideArgs& a, int n_utts, int max_frames, hipStream_t s);
+hipError_t launch_wide_unpack_covar(const float* planes, int n_utts, int n_planes, int plane0, int C,
+                                    float* out, hipStream_t s);
+hipError_t launch_wide_unpack_weight(const float* wplanes, int n_utts, int C, float* w, hipStream_t s);
+
 // launchers (implemented in the kernel TUs)
 hipError_t launch_pass1(int C, bool dump, const Pass1Args& a, int n_items, hipStream_t s, bool pcm16 = false);
 hipError_t launch_pass1_mc(int C, const Pass1Args& a, int n_items, hipStream_t s);

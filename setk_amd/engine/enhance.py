@@ -10,7 +10,7 @@ engineering unit is the batch, not the utterance.
 import numpy as np
 
 from .. import _ffi
-from ._common import (_Engine, BEAMFORMER_KINDS, RANK1, Pcm16Frames, compute_vad_masks,
+from ._common import (_Engine, BEAMFORMER_KINDS, RANK1, Pcm16Frames, channels_and_size, compute_vad_masks,
                       host_samples)
 
 
@@ -20,10 +20,13 @@ class BatchEnhancer(_Engine):
     def __init__(self, beamformer="mvdr", frame_len=512, frame_hop=256, center=True,
                  round_power_of_two=True, window="hann", ban=False, pmwf_ref=-1, rank1_appro="",
                  post_mask=False, vad_proportion=1, pcm16=False, device=None, ctx=None,
-                 max_batch_samples=1 << 28, strict_reference=False):
+                 max_batch_samples=1 << 28, strict_reference=False, max_wide_bytes=3 << 30):
         """strict_reference: refuse (status SETK_NUM_SINGULAR -> the CLI's LinAlgError branch)
         exactly where the reference's numpy.linalg.solve meets an exactly zero pivot
-        (SETK_FLAG_STRICT_REFERENCE, include/setk_hip.h); default: regularise and go through."""
+        (SETK_FLAG_STRICT_REFERENCE, include/setk_hip.h); default: regularise and go through.
+        max_wide_bytes: 9 to 16 channels keep their spectra on the device between the stages of
+        the batched call; a batch is cut where what its utterances take (_wide_bytes) would pass
+        this."""
         if beamformer not in BEAMFORMER_KINDS:
             raise ValueError(f"unknown beamformer {beamformer}")
         # no GPU / no library: setk_create fails here, loudly (there is no CPU fallback).
@@ -55,6 +58,7 @@ class BatchEnhancer(_Engine):
             _ffi.env_atoi("SETK_MC_PASS2", 1) != 0 and _ffi.env_atoi("SETK_LEGACY_FFT", 0) == 0
         self.vad_proportion = vad_proportion
         self.max_batch_samples = max_batch_samples
+        self.max_wide_bytes = max_wide_bytes
 
     def frames_and_length(self, num_samples):
         """(T, L) of the planned transform for a signal of num_samples, evaluated on
@@ -96,13 +100,44 @@ class BatchEnhancer(_Engine):
         samps = [u[0] for u in utts]
         groups = self._by_channels(samps, also=[u[2] is not None for u in utts])
         for (C, has_itf), idx in groups.items():
-            for batch in self._batches(idx, samps, self.max_batch_samples):
+            if self._wide(C):
+                batches = self._wide_batches(idx, samps, C)
+            else:
+                batches = self._batches(idx, samps, self.max_batch_samples)
+            for batch in batches:
                 self._run(utts, batch, C, has_itf, results)
         return results
 
+    def _wide(self, C):
+        """9 to 16 channels on the 512-point transform go through the batched call's wide path
+        (csrc/wide.hip); the VAD filter needs the spectrogram on the host and stays unfused."""
+        return self.n_fft == 512 and 8 < C <= 16 and not (0.5 < self.vad_proportion < 1)
+
+    def _wide_bytes(self, samps, C):
+        """What an utterance of the wide path takes on the device: samples, two masks, the wave,
+        and the call's scratch as include/setk_hip.h states it -- the bin-major spectra, the
+        beamformed spectrogram, a covariance slab per 128 frames, the planes and the weights."""
+        n = channels_and_size(samps)[1]
+        T, L = self.frames_and_length(n // C)
+        F, Tp, slabs = self.num_bins, (T + 3) & ~3, -(-T // 128)
+        scratch = 8 * F * C * Tp + 8 * T * F + slabs * F * 824 * 4 + 264 * 4 * (6 * 136 + 2 * 16) + 4 * L
+        return 4 * n + 2 * 4 * T * F + 4 * L + scratch
+
+    def _wide_batches(self, idx, samps, C):
+        batch, load = [], 0
+        for i in idx:
+            n = self._wide_bytes(samps[i], C)
+            if batch and load + n > self.max_wide_bytes:
+                yield batch
+                batch, load = [], 0
+            batch.append(i)
+            load += n
+        if batch:
+            yield batch
+
     def _run_unfused(self, utts, batch, C, has_itf, results):
-        """n_fft != 512 or more than 8 channels: the same stages through the
-        stand-alone operators (setk_stft -> setk_covar x2 -> setk_weights ->
+        """n_fft != 512, more than 16 channels, or 9 to 16 with the VAD filter: the same stages
+        through the stand-alone operators (setk_stft -> setk_covar x2 -> setk_weights ->
         setk_beamform -> setk_istft), everything resident on the device, one
         utterance at a time."""
         torch, ctx, dev, F = self.torch, self.ctx, self.dev, self.num_bins
@@ -150,8 +185,8 @@ class BatchEnhancer(_Engine):
             results[i] = (self._unfused_tail(enh, T, a), 0)
 
     def _run(self, utts, batch, C, has_itf, results):
-        if self.n_fft != 512 or C > 8:
-            # the fused kernels are specialised for n_fft = 512 and C <= 8
+        if self.n_fft != 512 or (C > 8 and not self._wide(C)):
+            # the batched call is specialised for n_fft = 512 and C <= 16 (9 to 16: csrc/wide.hip)
             return self._run_unfused(utts, batch, C, has_itf, results)
         kind = self.opts_kw["kind"]
         if has_itf and kind == _ffi.BF_MPDR_WHITEN:
@@ -163,7 +198,7 @@ class BatchEnhancer(_Engine):
         audio, masks, itfs, waves, ns = [], [], [], [], []
         flags = self.base_flags | (0 if has_itf else _ffi.FLAG_CLAMP_MASK)
         # 16-bit PCM all the way into the kernels (SETK_FLAG_IN_PCM16): no float32 copy exists
-        direct = self.pcm_direct_ok and all(isinstance(utts[i][0], Pcm16Frames) for i in batch) \
+        direct = self.pcm_direct_ok and C <= 8 and all(isinstance(utts[i][0], Pcm16Frames) for i in batch) \
             and not (0.5 < self.vad_proportion < 1)
         if direct:
             flags |= _ffi.FLAG_IN_PCM16

@@ -340,7 +340,7 @@ def run_offline(args, shard):
     if _fast_path_ok(args) and shard.torch_free_ok:
         # the streaming pipeline gets its buffers, streams and events from the library: a
         # single-process run never imports torch (0.9 s of a 2 s run on 192 utterances)
-        # (more than 8 channels run the unfused engine through torch tensors)
+        # (more than 8 channels run the engine's torch path: the batched call's wide form)
         _ffi.set_torch_free(wav_reader.first_channels_at_most(8))
     engine = BatchEnhancer(beamformer=args.beamformer, **stft_kwargs(args),
                            ban=bool(args.ban), pmwf_ref=args.pmwf_ref,
@@ -419,7 +419,7 @@ def _run_pipeline(args, engine, writer, wav_reader, tgt, itf, keys):
     import time
     marks, t_start = getattr(args, "_marks", {}), getattr(args, "_t_start", time.perf_counter())
     marks["pipeline_built"] = round(time.perf_counter() - t_start, 4)
-    wide = []  # more than 8 channels: stand-alone operators, after the pipeline drained
+    wide = []  # more than 8 channels: the engine's batched wide path, after the pipeline drained
     try:
         for key in keys:
             if key not in tgt:
