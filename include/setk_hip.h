@@ -718,6 +718,45 @@ int setk_ns_batch(setk_handle_t h, const setk_ns_opts* opts, int n_utts, const v
  * underflows (x > 745). */
 int setk_expint_e1(setk_handle_t h, const double* x, double* y, int n, void* stream);
 
+/* ---- SI-SNR scoring (scripts/sptk/libs/metric.py, compute_si_snr.py) --------
+ * si_snr (libs/metric.py:13-33): with x' = x - mean(x), s' = s - mean(s) (remove_dc), a = <x', s'> /
+ * (|s'|^2 + eps) and n = x' - a s' formed per sample, 20 log10(|a s'| / (|n| + eps) + eps).
+ * permute_si_snr (:36-60): the largest of sum_n si_snr(x[n], s[order[n]]) / K over
+ * itertools.permutations(range(K)) in its order, summed left to right from 0, and that order (the
+ * first on ties, np.argmax).  Float64 sums on the samples as given, where the reference computes
+ * in float32; every sum has one owner and a fixed order, so an utterance has the same bits in any
+ * batch.  A silent or constant signal and num_samples = 1 give 20 log10(eps). */
+#define SETK_FLAG_KEEP_DC 0x100 /* si_snr(remove_dc=False): the means stay in                     */
+
+/* si_snr (libs/metric.py:13-33) for every (estimate, reference) pair of every utterance and
+ * permute_si_snr (:36-60) over them; the loop bodies of compute_si_snr.py:80-105 for a batch.
+ *   num_src[u]     K_u estimates and K_u references, 1 <= K_u <= 8 (beyond: SETK_ERR_UNSUPPORTED,
+ *                  the search walks K! orders)
+ *   est / ref      sum(num_src) device pointers, utterance-major: float32 samples, or with
+ *                  SETK_FLAG_IN_PCM16 int16 samples as the wave file stores them (v / 32768, the
+ *                  same bits as the float32 form of those samples)
+ *   *_stride       the distance between samples of a signal: 1 for a mono buffer, C for channel 0
+ *                  of interleaved N x C frames (compute_si_snr.py:36 scores wave[0])
+ *   num_samples[u] one length per utterance, >= 1
+ *   pair           sum(num_src^2) float64: pair[i * K + j], estimate i against reference j
+ *   best           n_utts float64, may be NULL;  perm: sum(num_src) int, the chosen order, may be NULL
+ *   status[u]      SETK_NUM_NONFINITE for NaN / inf among the utterance's samples, may be NULL
+ * flags: SETK_FLAG_IN_PCM16 | SETK_FLAG_KEEP_DC, anything else is SETK_ERR_INVALID.  The tables
+ * num_src, est, ref, the strides and num_samples are HOST arrays; pair, best, perm and status host
+ * or device.  Six launches for the batch whatever its size (four with SETK_FLAG_KEEP_DC), scratch
+ * from the handle's arena; the call returns when the work has run.  With setk_set_profiling the
+ * stage times of setk_last_stage_ms are out[0] the means, out[1] the centred Gram sums, out[2] the
+ * residuals, out[3] the table, the search and the copies. */
+int setk_si_snr_batch(setk_handle_t h, int n_utts, const int* num_src, const void* const* est,
+                      const int* est_stride, const void* const* ref, const int* ref_stride,
+                      const int* num_samples, double eps, int flags, double* pair, double* best,
+                      int* perm, int* status, void* stream);
+
+/* One pair of host or device vectors of num_samples samples: what libs.metric.si_snr calls
+ * (libs/metric.py:13-33); out one float64, host or device.  Flags as above. */
+int setk_si_snr(setk_handle_t h, const float* x, const float* s, int num_samples, double eps, int flags,
+                double* out, void* stream);
+
 /* ---- data simulation: scripts/sptk/wav_simulate.py -------------------------
  * Reverberation, mixing at an SDR / SNR and peak normalisation of far-field training data.
  * Float32 data, float64 sums and coefficients. */

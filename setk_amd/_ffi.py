@@ -315,6 +315,15 @@ PROTOTYPES.update(
     setk_expint_e1=(I, [H, P, P, I, S]),
 )
 
+# ---- SI-SNR scoring ----
+FLAG_KEEP_DC = 256  # si_snr(remove_dc=False)
+METRIC_MAX_SOURCES = 8  # the search walks K! orders
+
+PROTOTYPES.update(
+    setk_si_snr_batch=(I, [H, I, IP, PP, IP, PP, IP, IP, c_double, I, P, P, P, P, S]),
+    setk_si_snr=(I, [H, P, P, I, c_double, I, P, S]),
+)
+
 # ---- data simulation ----
 SIMU_MAX_TAPS, SIMU_MAX_CHANNELS = 16384, 16
 SIMU_REPEAT = 1
@@ -956,6 +965,27 @@ class Context:
         """y = E1(x), float64 (numpy arrays or device tensors of the same size)."""
         n = x.size if isinstance(x, np.ndarray) else x.numel()
         self._run("setk_expint_e1", _ptr(x), _ptr(y), int(n), stream=stream)
+
+    # -- SI-SNR scoring ---------------------------------------------------------------
+    def si_snr_batch(self, num_src, est_ptrs, est_strides, ref_ptrs, ref_strides, num_samples, pair, best=None,
+                     perm=None, status=None, eps=1e-8, flags=0, stream=None):
+        """si_snr of every (estimate, reference) pair of every utterance and permute_si_snr over
+        them (libs/metric.py:13-60).  num_src: K_u per utterance; est_ptrs / ref_ptrs: sum(K_u)
+        device addresses, utterance-major, with their sample strides; pair float64 [sum K_u^2],
+        best float64 [n], perm int32 [sum K_u], status int32 [n] (numpy arrays or device
+        addresses; all but pair may be None).  flags: FLAG_IN_PCM16 | FLAG_KEEP_DC."""
+        n, m = len(num_src), len(est_ptrs)
+        self._run("setk_si_snr_batch", n, _ints(num_src), _ptrs(est_ptrs), _ints(est_strides, m), _ptrs(ref_ptrs, m),
+                  _ints(ref_strides, m), _ints(num_samples, n), float(eps), int(flags), _ptr(pair), _ptr(best),
+                  _ptr(perm), _ptr(status), stream=stream)
+
+    def si_snr(self, x, s, eps=1e-8, flags=0, stream=None):
+        """si_snr of one pair of float32 vectors (int16 with FLAG_IN_PCM16; numpy arrays or device
+        tensors of one size): a Python float."""
+        n = x.size if isinstance(x, np.ndarray) else x.numel()
+        out = np.empty(1, dtype=np.float64)
+        self._run("setk_si_snr", _ptr(x), _ptr(s), int(n), float(eps), int(flags), _ptr(out), stream=stream)
+        return float(out[0])
 
     # -- data simulation ------------------------------------------------------------
     def fir_reverb(self, spk, S, rir, N, R, out, power0=None, flags=0, stream=None):

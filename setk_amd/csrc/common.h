@@ -482,4 +482,34 @@ hipError_t launch_simu_peak(const SimuMix* d_mixes, int n_mix, int max_channels,
 hipError_t launch_simu_out(const SimuMix* d_mixes, int n_mix, int max_channels, int max_len, bool pcm16,
                            hipStream_t s);
 
+// SI-SNR scoring with permutation alignment (metric.hip): K estimates against K references per
+// utterance, float64 sums over tiles of kMetricTile samples, one owner per sum.
+constexpr int kMetricMaxSrc = 8;      // K <= 8: 8! = 40 320 orders per utterance
+constexpr int kMetricTile = 8192;     // samples of every signal per (utterance, tile) workgroup
+constexpr int kMetricThreads = 256;
+struct MetricUtt {
+    const void* sig[2 * kMetricMaxSrc];  // estimates at [0, K), references at [8, 8 + K); float32 or int16
+    int stride[2 * kMetricMaxSrc];       // in samples (C for channel 0 of interleaved frames)
+    int K, L;
+    int tile0, ntiles;  // this utterance's rows of the partial slab
+    double* mean;       // [16], the slots of sig
+    double* gram;       // [8] e_j | [64] d_ij | [64] a_ij  (pitch 8)
+    double* pair;       // [K][K] si_snr(estimate i, reference j)
+    double* best;       // or null
+    int* perm;          // [K] or null
+    int* status;
+};
+struct MetricItem { int utt, tile; };
+// quantities per row of the partial slab for the launch's padded source count KP (2, 4 or 8)
+__host__ __device__ constexpr int metric_row(int kp) { return kp * kp + kp; }
+int metric_padded_sources(int max_k);
+hipError_t launch_metric_means(const MetricUtt* d_utts, const MetricItem* d_items, int n_items, int n_utts, int kp,
+                               bool pcm16, double* d_partial, hipStream_t s);
+hipError_t launch_metric_gram(const MetricUtt* d_utts, const MetricItem* d_items, int n_items, int n_utts, int kp,
+                              bool pcm16, double eps, double* d_partial, int* d_flags, hipStream_t s);
+hipError_t launch_metric_residual(const MetricUtt* d_utts, const MetricItem* d_items, int n_items, int kp,
+                                  bool pcm16, double* d_partial, hipStream_t s);
+hipError_t launch_metric_search(const MetricUtt* d_utts, int n_utts, int kp, double eps, const double* d_partial,
+                                hipStream_t s);
+
 }  // namespace setk

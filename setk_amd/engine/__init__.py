@@ -17,3 +17,4 @@ from .spatial import BatchSpatialFeatures  # noqa: F401
 from .ns import BatchNoiseSuppressor  # noqa: F401
 from .simu import BatchSimulator  # noqa: F401
 from .online import BatchOnlineEnhancer  # noqa: F401
+from .metric import BatchSiSnr  # noqa: F401
