@@ -17,6 +17,7 @@ import os
 import numpy as np
 import pytest
 
+import covar_cases as cc
 import stft_cases as sc
 from conftest import rel_rms
 
@@ -429,8 +430,7 @@ def test_matrix_core_pass1_covariances(C):
             X32 = np.transpose(sc.f32_stft(utts[i], geo), (0, 2, 1))
             q = 2.0 ** -34 * np.sqrt(512) * sc.fullscale_of(case.peak)
             floor = 2 * np.sqrt(C) * q * np.linalg.norm(np.abs(X).max(axis=(0, 2)))
-            nrm = np.linalg.norm(X, axis=1)                                        # [C][T]
-            at = np.sqrt(((np.maximum(np.linalg.norm(X32 - X, axis=1), sc.U32 * nrm) + sc.mc_floor(case.peak)) ** 2)
+            at = np.sqrt((cc.forward_promise(X, X32, floor=sc.mc_floor(case.peak), axis=1) ** 2)
                          .sum(axis=0))                                             # [T]
             xf = np.linalg.norm(X, axis=0)                                         # [F][T]
             for name, got, mk in (("Rs", Rs[i], masks[i]), ("Rn", Rn[i], 1 - masks[i])):
@@ -441,7 +441,7 @@ def test_matrix_core_pass1_covariances(C):
                                                 yard.reshape(1, -1), floor=floor, exact_zero=False,
                                                 u_min=3 * sc.U32))
                 mk64 = mk.astype(np.float64).T                                     # [F][T]
-                per_bin = (mk64 * 2 * xf * at[None, :]).sum(axis=1) / np.maximum(mk64.sum(axis=1), 1e-6)
+                per_bin = cc.bin_forward_term(mk64, xf, at)
                 err = np.linalg.norm(got - ref, axis=1)
                 allow = sc.M_BITS * (np.linalg.norm(yard - ref, axis=1) + per_bin)
                 worst = int(np.argmax(err / allow))
