@@ -842,6 +842,72 @@ int setk_simu_num_channels(const setk_simu_recipe* r);
 int setk_simu_batch(setk_handle_t h, int n_mix, const setk_simu_recipe* recipes, int* status, int flags,
                     void* stream);
 
+/* ---- room impulse responses by the image method: include/rir-generator.{h,cc}, src/rir-simulate.cc,
+ * scripts/sptk/rir_generate_{1d,2d}.py ------------------------------------------
+ * RirGenerator::GenerateRir (rir-generator.cc:108-192) with MicrophoneSim (:194-223): per
+ * microphone every image (x, y, z, q, j, k) of the source within |x| <= nx = ceil(num_samples /
+ * (2 T.x)) (likewise y, z; T the room in samples) that passes the reflection-order test (:153-155)
+ * and floor(dist) < num_samples (:158) adds a Tw = 2 int(0.004 fs + 0.5) tap Hann-windowed sinc at
+ * pos = floor(dist) - Tw / 2 + 1, clipped to [0, num_samples), with the gain mic(p) Refl / (4 pi dist
+ * cts), cts = c / fs; then the optional second-order high-pass recursion (:180-190).
+ * Arithmetic: the inputs are the reference's float32 values; geometry, fractional delay and the
+ * sums are float64 (the reference: float32 throughout), rounded to float32 once at the end.  The
+ * sums are kept in 64-bit fixed point (2^-40): integer adds do not depend on their order, so a RIR
+ * has the same bits run to run, alone or in any batch, however its images are split over
+ * workgroups.  tests/PARITY_NOTES_RIR.md has the measured distances. */
+#define SETK_RIR_MAX_TAPS 16384
+#define SETK_RIR_MAX_MICS 16
+#define SETK_RIR_MIC_BIDIRECTIONAL 0 /* the polar patterns of rir-generator.h:32-38, in their order */
+#define SETK_RIR_MIC_HYPERCARDIOID 1
+#define SETK_RIR_MIC_CARDIOID 2
+#define SETK_RIR_MIC_SUBCARDIOID 3
+#define SETK_RIR_MIC_OMNIDIRECTIONAL 4
+#define SETK_RIR_NO_SPLIT 0x1 /* flags: one workgroup walks all images of a (RIR, microphone) pair */
+
+/* One RIR: RirGeneratorOptions (rir-generator.h:63-113) after ComputeDerived (rir-generator.cc:25-106)
+ * has parsed it.  A reverberation time is turned into coefficients by the caller (:78-92 in the
+ * reference's float32 steps: setk_amd.libs.rir.beta_from_rt60).  The arrays are HOST memory. */
+typedef struct setk_rir_spec {
+    const float* room;   /* [3] --room-topo, metres                                             */
+    const float* source; /* [3] --source-location                                               */
+    const float* mics;   /* [n_mics][3] --receiver-location                                     */
+    const float* beta;   /* [n_beta] the reflection coefficients; n_beta must be 6 (:98)        */
+    const float* angle;  /* [2] --angle: azimuth, elevation (radians), or NULL for 0, 0         */
+    int n_mics;          /* 1 .. SETK_RIR_MAX_MICS                                              */
+    int n_beta;
+    int mic_type;        /* SETK_RIR_MIC_*                                                      */
+    int order;           /* --order, -1: every image                                            */
+    int num_samples;     /* --number-samples, 1 .. SETK_RIR_MAX_TAPS                            */
+    int hp_filter;       /* --hp-filter                                                         */
+    float samp_frequency, sound_velocity;
+} setk_rir_spec;
+
+/* GenerateRir for a ragged batch of RIRs: microphone counts, tap counts and rooms differ freely.
+ *   out[r]     [n_mics][num_samples] float32, host or device: the generator's matrix, unscaled
+ *              (the * 32767 of rir-simulate.cc:64 is the writer's business)
+ *   status[r]  host or device, or NULL: SETK_NUM_NONFINITE for NaN / inf among the RIR's inputs
+ *              or an image whose gain is not below 2^10 (a source on a microphone; the reference
+ *              writes inf / NaN taps there); such an image is left out, the other RIRs of the batch
+ *              are not touched
+ * flags: SETK_RIR_NO_SPLIT.  specs and out are HOST arrays of n_rirs entries.  Two launches for the
+ * batch (the images; the fold of the parts, the high-pass recursion and the rounding), scratch
+ * from the handle's arena (8 bytes per tap and part); the call returns when the work has run.
+ * SETK_ERR_UNSUPPORTED outside 1 to 16 microphones and 1 to 16384 taps (what setk_simu_batch takes
+ * RIRs at), for samp_frequency above 64 kHz (Tw > 512) and more than 2^31 - 1 images per
+ * microphone; SETK_ERR_INVALID for what the reference asserts (rir-generator.cc:29-31, :98):
+ * samp_frequency < 1, sound_velocity < 1, order < -1, n_beta != 6, an unknown mic_type, and a room
+ * dimension that is not positive.  With setk_set_profiling the stage times of
+ * setk_last_stage_ms are out[0] the tables, out[1] the images, out[2] fold + high-pass, out[3] the
+ * copies. */
+int setk_rir_generate_batch(setk_handle_t h, int n_rirs, const setk_rir_spec* specs, float* const* out,
+                            int* status, int flags, void* stream);
+
+/* One RIR (what rir-simulate computes for one command line, rir-simulate.cc:54-59): out
+ * [n_mics][num_samples] float32 and status (one int, may be NULL), host or device.  The bits of the
+ * batch call. */
+int setk_rir_generate(setk_handle_t h, const setk_rir_spec* spec, float* out, int* status, int flags,
+                      void* stream);
+
 /* ---- fused hot path ------------------------------------------------------
  * The compute body of apply_adaptive_beamformer.py:130-178 for a batch of
  * utterances that share the channel count, in four kernel stages:

@@ -391,6 +391,48 @@ PROTOTYPES.update(
     setk_simu_batch=(I, [H, I, POINTER(SimuRecipe), P, I, S]),
 )
 
+# ---- room impulse responses by the image method ----
+RIR_MAX_TAPS, RIR_MAX_MICS = 16384, 16
+RIR_MIC_BIDIRECTIONAL, RIR_MIC_HYPERCARDIOID, RIR_MIC_CARDIOID, RIR_MIC_SUBCARDIOID = 0, 1, 2, 3
+RIR_MIC_OMNIDIRECTIONAL = 4
+RIR_MIC_TYPES = {"bidirectional": 0, "hypercardioid": 1, "cardioid": 2, "subcardioid": 3, "omnidirectional": 4}
+RIR_NO_SPLIT = 1  # one workgroup walks all images of a (RIR, microphone) pair
+
+
+class RirSpec(ctypes.Structure):
+    _fields_ = [("room", POINTER(c_float)), ("source", POINTER(c_float)), ("mics", POINTER(c_float)),
+                ("beta", POINTER(c_float)), ("angle", POINTER(c_float)), ("n_mics", c_int), ("n_beta", c_int),
+                ("mic_type", c_int), ("order", c_int), ("num_samples", c_int), ("hp_filter", c_int),
+                ("samp_frequency", c_float), ("sound_velocity", c_float)]
+
+
+def rir_spec(room, source, mics, beta, num_samples, samp_frequency=16000.0, sound_velocity=340.0, order=-1,
+             hp_filter=True, mic_type="omnidirectional", angle=None):
+    """setk_rir_spec over float32 copies of the arrays (the structure keeps them alive): room and
+    source 3 values, mics n x 3, beta the reflection coefficients (six; any other count is passed on
+    for the library to refuse), angle None or (azimuth, elevation)."""
+    if mic_type not in RIR_MIC_TYPES:
+        raise ValueError(f"Unknown option values: --microphone-type={mic_type}")
+    mics = np.ascontiguousarray(mics, dtype=np.float32).reshape(-1, 3)
+    keep = dict(room=np.ascontiguousarray(room, dtype=np.float32).reshape(3),
+                source=np.ascontiguousarray(source, dtype=np.float32).reshape(3), mics=mics,
+                beta=np.ascontiguousarray(beta, dtype=np.float32).reshape(-1))
+    if angle is not None:
+        keep["angle"] = np.ascontiguousarray(angle, dtype=np.float32).reshape(2)
+    sp = RirSpec(n_mics=mics.shape[0], n_beta=keep["beta"].size, mic_type=RIR_MIC_TYPES[mic_type], order=int(order),
+                 num_samples=int(num_samples), hp_filter=1 if hp_filter else 0,
+                 samp_frequency=float(samp_frequency), sound_velocity=float(sound_velocity))
+    for name, a in keep.items():
+        setattr(sp, name, a.ctypes.data_as(POINTER(c_float)))
+    sp._keep = keep
+    return sp
+
+
+PROTOTYPES.update(
+    setk_rir_generate_batch=(I, [H, I, POINTER(RirSpec), PP, P, I, S]),
+    setk_rir_generate=(I, [H, POINTER(RirSpec), P, P, I, S]),
+)
+
 
 # ---- fused hot path; the RCCL barrier; stage timings ----
 class BatchTaps(ctypes.Structure):
@@ -1000,6 +1042,22 @@ class Context:
         (numpy or device address) or None."""
         n = len(recipes)
         self._run("setk_simu_batch", n, (SimuRecipe * n)(*recipes), _ptr(status), int(flags), stream=stream)
+
+    # -- room impulse responses -----------------------------------------------------
+    def rir_generate_batch(self, specs, outs, status=None, flags=0, stream=None):
+        """GenerateRir for a list of rir_spec structures; outs[r] float32 [n_mics][num_samples] (numpy
+        arrays or device addresses), status int32[n] (numpy or device address) or None."""
+        n = len(specs)
+        self._run("setk_rir_generate_batch", n, (RirSpec * n)(*specs), _ptrs(outs, n), _ptr(status), int(flags),
+                  stream=stream)
+
+    def rir_generate(self, spec, out=None, flags=0, stream=None):
+        """One RIR: (float32 [n_mics][num_samples], its SETK_NUM_* status)."""
+        if out is None:
+            out = np.empty((spec.n_mics, spec.num_samples), dtype=np.float32)
+        status = np.zeros(1, dtype=np.int32)
+        self._run("setk_rir_generate", ctypes.byref(spec), _ptr(out), _ptr(status), int(flags), stream=stream)
+        return out, int(status[0])
 
     # -- fused hot path ---------------------------------------------------------
     def enhance_batch(self, opts, num_channels, audio_ptrs, num_samples, mask_ptrs,

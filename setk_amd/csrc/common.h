@@ -512,4 +512,35 @@ hipError_t launch_metric_residual(const MetricUtt* d_utts, const MetricItem* d_i
 hipError_t launch_metric_search(const MetricUtt* d_utts, int n_utts, int kp, double eps, const double* d_partial,
                                 hipStream_t s);
 
+// Room impulse responses by the image method (rir.hip): one channel is a (RIR, microphone) pair,
+// its images are cut into parts, each part's workgroup sums its taps in 64-bit fixed point in LDS.
+constexpr int kRirMaxTaps = 16384;   // = SETK_RIR_MAX_TAPS
+constexpr int kRirMaxMics = 16;      // = SETK_RIR_MAX_MICS
+constexpr int kRirMaxWindow = 512;   // Tw = 2 int(0.004 fs + 0.5): fs up to 64 kHz
+constexpr int kRirThreads = 512;     // of the images kernel
+constexpr int kRirFixShift = 40;     // a tap is an integer multiple of 2^-40
+struct RirChan {
+    double S[3], T[3], R[3];  // source, room, microphone in samples (metres / cts)
+    double beta[6];
+    double u[3];              // the pattern's look direction: gain = rho + (1 - rho) u.p / |p|
+    double rho;               // 1: omnidirectional
+    double cts;
+    double hp[4];             // B1, B2, A1, R1 of rir-generator.cc:121
+    long long* part;          // [nparts][ns] fixed-point sums
+    float* out;               // [ns]
+    int* status;              // of the RIR (its microphones share it)
+    int ns, order, Tw, hp_on;
+    int n[3];                 // nx, ny, nz
+    int bad;                  // NaN / inf among the inputs: no image is walked
+    int nparts, pad_;
+};
+struct RirItem {
+    int chan, part;
+    long long img0, img1;     // images [img0, img1) in the reference's loop order (x, y, z, q, j, k)
+};
+size_t rir_lds_bytes(int ns, int Tw);
+hipError_t launch_rir_images(const RirChan* d_chans, const RirItem* d_items, int n_items, int max_ns, int max_tw,
+                             hipStream_t s);
+hipError_t launch_rir_finish(const RirChan* d_chans, int n_chans, hipStream_t s);
+
 }  // namespace setk

@@ -18,3 +18,4 @@ from .ns import BatchNoiseSuppressor  # noqa: F401
 from .simu import BatchSimulator  # noqa: F401
 from .online import BatchOnlineEnhancer  # noqa: F401
 from .metric import BatchSiSnr  # noqa: F401
+from .rir import BatchRirGenerator  # noqa: F401
