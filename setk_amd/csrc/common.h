@@ -340,6 +340,29 @@ hipError_t launch_auxiva_spread_norm(const unsigned* norm_bits, int C, int n, un
 // direction-fastest ([F][K][ssl_apad(A)] complex64); scores per window float64 [W][A].
 constexpr int kSslMl = 0, kSslSrp = 1, kSslMusic = 2;  // = SETK_SSL_*
 constexpr int kSslTile = 32;
+
+// exp(i angle(z)) as np.angle has it, shared by ssl.hip and spatial.hip: angle(0) = 0, a NaN
+// component gives (NaN, NaN), every finite non-zero complex64 gives its phase.  |z|^2 is formed in
+// float32; where it leaves [2^-124, 2^124] (the squares underflow below |z| = 2^-63 and overflow
+// above 2^64) z is first rescaled by an exact power of two, which moves |z| into [2^-49, 2^59]
+// and not one bit of the phase.  Inside the range nothing is rescaled.  The rare cases all rejoin
+// the one straight line of square root, reciprocal and products (a zero as z = 1).
+__device__ __forceinline__ float2 phasor(float2 z) {
+    float n2 = z.x * z.x + z.y * z.y;
+    if (!(n2 >= 0x1p-124f && n2 <= 0x1p124f)) {
+        const float k = n2 > 0x1p124f ? 0x1p-70f : 0x1p100f;
+        z.x *= k;
+        z.y *= k;
+        n2 = z.x * z.x + z.y * z.y;
+        if (n2 == 0.f) {
+            z = make_float2(1.f, 0.f);
+            n2 = 1.f;
+        }
+    }
+    const float n = sqrtf(n2);
+    const float r = 1.f / n;
+    return make_float2(z.x * r, z.y * r);
+}
 struct SslUtt {         // one utterance of a prep / fold / frame-score launch
     const float* spec;  // [C][T][pitch] complex64
     const float* mask;  // [T][F] or null

@@ -27,15 +27,7 @@ constexpr int kTile = kSslTile;
 constexpr float kPi = 3.14159265358979323846f;
 constexpr float kEps = 1.1920929e-07f;  // np.finfo(np.float32).eps, the reference's EPSILON
 
-__device__ __forceinline__ float2 phasor(float2 z) {
-    // exp(i angle(z)); np.angle(0) = 0
-    const float n = sqrtf(z.x * z.x + z.y * z.y);
-    if (!(n > 0.f)) return make_float2(1.f, 0.f);
-    const float r = 1.f / n;
-    return make_float2(z.x * r, z.y * r);
-}
-
-// l conj(r) of two unit phasors: (cos, sin) of the phase difference
+// l conj(r) of two unit phasors (phasor(): common.h): (cos, sin) of the phase difference
 __device__ __forceinline__ float2 coherence(float2 l, float2 r) {
     return make_float2(l.x * r.x + l.y * r.y, l.y * r.x - l.x * r.y);
 }

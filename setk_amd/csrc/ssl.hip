@@ -21,14 +21,6 @@ namespace {
 constexpr int kTile = kSslTile;
 constexpr int kFoldChunk = 64;
 
-__device__ __forceinline__ float2 phasor(float2 z) {
-    // exp(i angle(z)); np.angle(0) = 0
-    const float n = sqrtf(z.x * z.x + z.y * z.y);
-    if (!(n > 0.f)) return make_float2(1.f, 0.f);
-    const float r = 1.f / n;
-    return make_float2(z.x * r, z.y * r);
-}
-
 // ---- steer vectors [A][C][F] -> [F][K][Apad], direction fastest, zero beyond A ----
 //   kSslMl:    sv / ||sv||_2 over the microphones (ssl.py:27), K = C
 //   kSslSrp:   exp(i (angle sv_l - angle sv_r)) per pair (ssl.py:66-70), K = P

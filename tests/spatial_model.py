@@ -43,12 +43,18 @@ def spec_of(stored):
 
 
 def phasor(x):
-    """exp(i angle(x)) in float32; angle(0) = 0."""
+    """exp(i angle(x)) in float32 as common.h's phasor() forms it; angle(0) = 0, a NaN stays a NaN,
+    and a cell whose squared modulus leaves [2^-124, 2^124] is rescaled by a power of two first."""
     x = np.asarray(x, dtype=np.complex64)
     re, im = x.real.astype(f32), x.imag.astype(f32)
-    n = np.sqrt(re * re + im * im, dtype=f32)
-    r = np.where(n > 0, f32(1) / np.where(n > 0, n, f32(1)), f32(0)).astype(f32)
-    return np.where(n > 0, re * r, f32(1)).astype(f32), np.where(n > 0, im * r, f32(0)).astype(f32)
+    with np.errstate(over="ignore", under="ignore", invalid="ignore"):
+        n2 = re * re + im * im
+        outside = ~((n2 >= f32(2.0 ** -124)) & (n2 <= f32(2.0 ** 124)))
+        k = np.where(outside, np.where(n2 > f32(2.0 ** 124), f32(2.0 ** -70), f32(2.0 ** 100)), f32(1)).astype(f32)
+        re, im = re * k, im * k
+        n = np.sqrt(np.where(outside, re * re + im * im, n2), dtype=f32)
+        r = (f32(1) / np.where(n == 0, f32(1), n)).astype(f32)
+        return np.where(n == 0, f32(1), re * r).astype(f32), np.where(n == 0, f32(0), im * r).astype(f32)
 
 
 def coherence(xl, xr):
