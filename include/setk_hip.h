@@ -561,7 +561,8 @@ typedef struct setk_ssl_opts {
  *   score   [W][A] float64 or NULL, index [W] int32: the lowest index attaining the extremum,
  *           as np.argmax / np.argmin choose
  *   status  one int or NULL: MUSIC, the worst setk_pevd status over bins and windows (a bin
- *           whose covariance is zero has no defined eigenvector); 0 for the other backends
+ *           whose covariance is zero has no defined eigenvector: SETK_NUM_SINGULAR); 0 for the
+ *           other backends
  * All data pointers host or device.  Any A, T, F; SETK_ERR_UNSUPPORTED outside 1 <= C <= 16. */
 int setk_ssl_scores(setk_handle_t h, const setk_ssl_opts* opts, const float* spec, const float* mask,
                     const float* steer_vector, int num_doas, int num_channels, int num_frames,

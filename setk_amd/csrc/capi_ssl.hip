@@ -86,7 +86,8 @@ int ssl_run(setk_handle_t h, const setk_ssl_opts& o, int C, int F, int A, const 
                 HIP_TRY(h, launch_covar_spec(C, xo, m2, Tw, F, part, split, s));
                 HIP_TRY(h, launch_covar_spec_finalize(C, part, used, F, cov, s));
                 SETK_TRY(pevd_in_arena(h, cov, F, C, pv, d_st + (size_t)w0 * F, s));
-                HIP_TRY(h, launch_ssl_music_score(svt, pv, A, F, C, d_score + (size_t)w0 * A, s));
+                HIP_TRY(h, launch_ssl_music_score(svt, pv, cov, A, F, C, d_score + (size_t)w0 * A,
+                                                  d_st + (size_t)w0 * F, s));
                 arena_rewind(h, mark);
             }
         SETK_TRY(profile_mark(h, 2, s));

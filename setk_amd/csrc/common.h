@@ -392,8 +392,9 @@ hipError_t launch_ssl_frame_scores(const SslUtt* d_utts, const float* svt, int m
                                    int F, int K, float inv1pe, float eps, float compression, hipStream_t s);
 hipError_t launch_ssl_music_prep(const float* spec, const float* mask, int C, int T, int F, int pitch, int t0, int t1,
                                  float* xo, float* m2, hipStream_t s);
-hipError_t launch_ssl_music_score(const float* svt, const float* v, int A, int F, int C, double* score,
-                                  hipStream_t s);
+// (cov [F][C][C] complex64: a zero bin is reported in status [F], SETK_NUM_SINGULAR)
+hipError_t launch_ssl_music_score(const float* svt, const float* v, const float* cov, int A, int F, int C,
+                                  double* score, int* status, hipStream_t s);
 hipError_t launch_ssl_windows(const SslWin* d_wins, int n_wins, int A, bool take_min, double* score, int* index,
                               hipStream_t s);
 

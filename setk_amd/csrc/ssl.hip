@@ -13,6 +13,7 @@
 // floats per (bin, k) at a wave-uniform address, which the compiler turns into scalar loads --
 // the multiply-adds then take x from scalar registers and no LDS is involved.
 #include "common.h"
+#include "../../include/setk_hip.h"
 
 namespace setk {
 
@@ -83,9 +84,16 @@ __global__ __launch_bounds__(256) void ssl_obs_prep_kernel(const SslUtt* __restr
                 if (MODE == kSslMl) {
                     v = spec[(size_t)k * chan + at];
                     if (norm) {  // stft / np.maximum(|stft|, eps)  (ssl.py:29)
-                        const float r = 1.f / fmaxf(sqrtf(v.x * v.x + v.y * v.y), eps);
-                        v.x *= r;
-                        v.y *= r;
+                        const float n2 = v.x * v.x + v.y * v.y;
+                        if (n2 > 0x1p124f && eps <= 0x1p62f) {
+                            // the squares overflow above |v| = 2^64: |v| > eps here, so v / |v|
+                            // through phasor()'s exact rescaling
+                            v = phasor(v);
+                        } else {
+                            const float r = 1.f / fmaxf(sqrtf(n2), eps);
+                            v.x *= r;
+                            v.y *= r;
+                        }
                     }
                     ssh[i] += v.x * v.x + v.y * v.y;
                 } else {  // mask x exp(i (angle x_l - angle x_r))  (ssl.py:64-68)
@@ -205,7 +213,7 @@ __global__ __launch_bounds__(64) void ssl_frame_score_kernel(const SslUtt* __res
                 const float delta = q[t] - (ar[t] * ar[t] + ai[t] * ai[t]) * inv1pe;  // ssl.py:33
                 float ll;
                 if (MODE == kMlLog)
-                    ll = -__logf(fmaxf(delta, eps));
+                    ll = -__logf(delta < eps ? eps : delta);  // (a NaN stays one, as np.maximum has it)
                 else
                     ll = -__expf(compression * __logf(delta));  // -delta^compression (NaN below 0, like numpy)
                 S[t] = fmaf(q[kTile + t], ll, S[t]);
@@ -229,9 +237,21 @@ __global__ __launch_bounds__(64) void ssl_frame_score_kernel(const SslUtt* __res
 }
 
 // ---- MUSIC: score[w][a] = sum_f | ||sv||^2 - |v_f^H sv|^2 |, v the principal eigenvector of
-// window w's covariance (I - v v^H is the noise-subspace projector of ssl.py:98-107) ----
+// window w's covariance (I - v v^H is the noise-subspace projector of ssl.py:98-107).  A bin whose
+// covariance [C][C] is zero has no principal eigenvector, which the eigen-solve does not say:
+// the first workgroup reports it beside that solve's status ----
 __global__ __launch_bounds__(64) void ssl_music_score_kernel(const float2* __restrict__ svt, const float* __restrict__ v,
-                                                             int A, int Apad, int F, int C, double* __restrict__ score) {
+                                                             const float2* __restrict__ cov, int A, int Apad, int F,
+                                                             int C, double* __restrict__ score, int* __restrict__ status) {
+    if (blockIdx.x == 0)
+        for (int f = threadIdx.x; f < F; f += 64) {
+            bool zero = true;
+            for (int e = 0; e < C * C; ++e) {
+                const float2 r = cov[(size_t)f * C * C + e];
+                zero = zero && r.x == 0.f && r.y == 0.f;
+            }
+            if (zero && status[f] == SETK_NUM_OK) status[f] = SETK_NUM_SINGULAR;
+        }
     const int a = blockIdx.x * 64 + threadIdx.x;
     const float2* __restrict__ sp = svt + a;
     double acc = 0.0;
@@ -378,11 +398,11 @@ hipError_t launch_ssl_music_prep(const float* spec, const float* mask, int C, in
     return hipGetLastError();
 }
 
-hipError_t launch_ssl_music_score(const float* svt, const float* v, int A, int F, int C, double* score,
-                                  hipStream_t s) {
+hipError_t launch_ssl_music_score(const float* svt, const float* v, const float* cov, int A, int F, int C,
+                                  double* score, int* status, hipStream_t s) {
     const int Apad = ssl_apad(A);
     hipLaunchKernelGGL(ssl_music_score_kernel, dim3(Apad / 64), dim3(64), 0, s, reinterpret_cast<const float2*>(svt),
-                       v, A, Apad, F, C, score);
+                       v, reinterpret_cast<const float2*>(cov), A, Apad, F, C, score, status);
     return hipGetLastError();
 }
 
