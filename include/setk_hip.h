@@ -719,6 +719,89 @@ int setk_ns_batch(setk_handle_t h, const setk_ns_opts* opts, int n_utts, const v
  * underflows (x > 745). */
 int setk_expint_e1(setk_handle_t h, const double* x, double* y, int n, void* stream);
 
+/* ---- oracle TF masks and mask-based separation -------------------------------
+ * scripts/sptk/compute_mask.py, wav_separate.py, oracle_separate.py.  float32 throughout, as the
+ * reference is once its spectra are complex64; |z| is cmat_abs (libs/utils.py:30-42), sqrt(re^2 +
+ * im^2); the cosine of a phase difference is formed without trigonometry.  A cell with an operand
+ * that is exactly zero follows numpy: np.angle(0) = 0, 0 / 0 = NaN, x / 0 = +-inf, and the clips
+ * hand a NaN on as np.minimum / np.maximum do. */
+#define SETK_TFMASK_IBM 0 /* |tgt| > |mix - tgt|                                           */
+#define SETK_TFMASK_IRM 1 /* |tgt| / sqrt(|tgt|^2 + |mix - tgt|^2 + eps)                   */
+#define SETK_TFMASK_IAM 2 /* |tgt| / |mix|                                                 */
+#define SETK_TFMASK_PSM 3 /* |tgt| cos(arg mix - arg tgt) / |mix|                          */
+#define SETK_TFMASK_PSA 4 /* |tgt| max(0, cos(arg mix - arg tgt))                          */
+#define SETK_TFMASK_CRM 5 /* tgt / (mix + eps), both parts through 10 tanh(0.05 x); [T][2F] */
+#define SETK_TFMASK_MAX_TARGETS 8
+/* what run() logs per utterance (compute_mask.py:136-152): cells above the cutoff, cells below
+ * zero after that clip, and the sum of the latter (float64, a fixed order: the same bits in any
+ * batch) */
+typedef struct setk_tfmask_stats {
+    long long over;
+    long long below;
+    double below_sum;
+} setk_tfmask_stats;
+
+/* compute_mask(tgt, mix, kind) (compute_mask.py:59-107) and the clips of run() (:136-152) --
+ * min(mask, cutoff) when cutoff > 0, then max(mask, 0), for every kind as the tool has it -- on
+ * stored spectra tgt, mix [T][F] complex64: mask [T][F] float32 ([T][2F] for SETK_TFMASK_CRM, real
+ * parts then imaginary parts).  A NaN cutoff leaves both clips out: the mask as compute_mask()
+ * itself returns it (the statistics are then zero).  All data pointers host or device; stats may
+ * be NULL.  Any T, F. */
+int setk_tf_mask(setk_handle_t h, int kind, const float* tgt, const float* mix, int num_frames,
+                 int num_bins, float cutoff, float* mask, setk_tfmask_stats* stats, void* stream);
+
+/* wav_separate.py:63-74 in front of the inverse: out = spec x mask, or with phase_ref
+ * |spec| x mask x exp(i angle(phase_ref)); spec, phase_ref, out [T][F] complex64, mask [T][F]
+ * float32, host or device; phase_ref may be NULL. */
+int setk_tf_apply(setk_handle_t h, const float* spec, const float* mask, const float* phase_ref,
+                  int num_frames, int num_bins, float* out, void* stream);
+
+/* The loop body of compute_mask.py:128-153 for a batch of (clean, noisy) pairs, n_fft = 512 plan:
+ * ONE launch transforms both signals of every frame and stores the mask alone.
+ *   tgt[u], mix[u]  device float32 [num_samples[u]] (one length per pair), or with
+ *                   SETK_FLAG_IN_PCM16 device int16 as the wave file stores it (x 2^-15 on the
+ *                   device, the bits of the float32 form)
+ *   mask[u]         device float32 [T_u][257] ([T_u][514] for crm)
+ *   stats           n_utts entries, host or device, or NULL
+ *   status[u]       SETK_NUM_NONFINITE when the mask holds NaN / inf (it is delivered all the
+ *                   same: the reference writes such masks too); host or device, or NULL
+ * The pointer tables and num_samples are HOST arrays; scratch from the handle's arena; the call
+ * returns when the work has run.  Every output value has one owner and a fixed order: an
+ * utterance has the same bits alone and in any batch.  With setk_set_profiling the stage times of
+ * setk_last_stage_ms are out[0] the fused forward, out[1] the statistics. */
+int setk_tf_mask_batch(setk_handle_t h, int kind, int n_utts, const void* const* tgt,
+                       const void* const* mix, const int* num_samples, float cutoff,
+                       float* const* mask, setk_tfmask_stats* stats, int* status, int flags,
+                       void* stream);
+
+/* The loop body of wav_separate.py:39-75 for a batch: one fused forward launch (the mixture, and
+ * the phase reference where given, transformed and masked in registers), one inverse-STFT launch,
+ * one scaling launch.
+ *   mix[u]        device samples as above;  phase_ref: NULL, or a table whose entries may be NULL
+ *   mask[u]       device float32 [T_u][257]
+ *   norm          HOST array or NULL: norm[u] > 0 scales the wave to that max-abs
+ *                 (inverse_stft(norm=), --use-mixed-norm), otherwise the wave stays as it is
+ *   nsamps        HOST array or NULL: nsamps[u] >= 0 is the wave's length (--keep-length),
+ *                 otherwise setk_istft_num_samples(T_u, -1)
+ *   wave[u]       device float32, or int16 with SETK_FLAG_OUT_PCM16
+ *   status[u]     SETK_NUM_NONFINITE for NaN / inf in the masked spectrum; host or device, or NULL
+ * Stage times: out[0] forward, out[1] inverse, out[2] scaling. */
+int setk_tf_separate_batch(setk_handle_t h, int n_utts, const void* const* mix,
+                           const void* const* phase_ref, const int* num_samples,
+                           const float* const* mask, const float* norm, const int* nsamps,
+                           void* const* wave, int* status, int flags, void* stream);
+
+/* The loop body of oracle_separate.py:65-82 for a batch with num_targets references per mixture:
+ * compute_mask (:19-45) for SETK_TFMASK_IBM / IRM / IAM / PSM (any other kind: SETK_ERR_INVALID,
+ * the tool's choices) and inverse_stft(mixture x mask_k) without norm.  One fused forward launch
+ * runs num_targets + 1 transforms per frame and stores the masked spectra alone; one inverse
+ * launch takes them as n_utts x num_targets utterances.  targets[u * K + k], wave[u * K + k];
+ * nsamps as above.  More than SETK_TFMASK_MAX_TARGETS targets: SETK_ERR_UNSUPPORTED. */
+int setk_oracle_separate_batch(setk_handle_t h, int kind, int n_utts, int num_targets,
+                               const void* const* mix, const void* const* targets,
+                               const int* num_samples, const int* nsamps, void* const* wave,
+                               int* status, int flags, void* stream);
+
 /* ---- SI-SNR scoring (scripts/sptk/libs/metric.py, compute_si_snr.py) --------
  * si_snr (libs/metric.py:13-33): with x' = x - mean(x), s' = s - mean(s) (remove_dc), a = <x', s'> /
  * (|s'|^2 + eps) and n = x' - a s' formed per sample, 20 log10(|a s'| / (|n| + eps) + eps).

@@ -315,6 +315,34 @@ PROTOTYPES.update(
     setk_expint_e1=(I, [H, P, P, I, S]),
 )
 
+# ---- oracle TF masks and mask-based separation ----
+TFMASK_IBM, TFMASK_IRM, TFMASK_IAM, TFMASK_PSM, TFMASK_PSA, TFMASK_CRM = range(6)
+TFMASK_MAX_TARGETS = 8
+TFMASK_NAMES = {"ibm": TFMASK_IBM, "irm": TFMASK_IRM, "iam": TFMASK_IAM, "psm": TFMASK_PSM, "psa": TFMASK_PSA,
+                "crm": TFMASK_CRM}
+ORACLE_MASKS = ("iam", "irm", "ibm", "psm")  # oracle_separate.py's choices
+
+
+class TfmaskStats(ctypes.Structure):
+    """setk_tfmask_stats: what compute_mask.py logs for one mask."""
+    _fields_ = [("over", ctypes.c_longlong), ("below", ctypes.c_longlong), ("below_sum", c_double)]
+
+
+def tfmask_kind(name):
+    try:
+        return TFMASK_NAMES[name]
+    except KeyError:
+        raise ValueError(f"unknown mask {name!r}: one of {sorted(TFMASK_NAMES)}") from None
+
+
+PROTOTYPES.update(
+    setk_tf_mask=(I, [H, I, P, P, I, I, c_float, P, P, S]),
+    setk_tf_apply=(I, [H, P, P, P, I, I, P, S]),
+    setk_tf_mask_batch=(I, [H, I, I, PP, PP, IP, c_float, PP, P, P, I, S]),
+    setk_tf_separate_batch=(I, [H, I, PP, PP, IP, PP, P, IP, PP, P, I, S]),
+    setk_oracle_separate_batch=(I, [H, I, I, I, PP, PP, IP, IP, PP, P, I, S]),
+)
+
 # ---- SI-SNR scoring ----
 FLAG_KEEP_DC = 256  # si_snr(remove_dc=False)
 METRIC_MAX_SOURCES = 8  # the search walks K! orders
@@ -1007,6 +1035,57 @@ class Context:
         """y = E1(x), float64 (numpy arrays or device tensors of the same size)."""
         n = x.size if isinstance(x, np.ndarray) else x.numel()
         self._run("setk_expint_e1", _ptr(x), _ptr(y), int(n), stream=stream)
+
+    # -- oracle TF masks and mask-based separation -----------------------------------
+    @staticmethod
+    def _stats_out(stats):
+        """[(over, below, below_sum), ...] of a TfmaskStats array."""
+        return [(int(s.over), int(s.below), float(s.below_sum)) for s in stats]
+
+    def tf_mask(self, kind, tgt, mix, T, F, mask, cutoff=-1.0, want_stats=True, stream=None):
+        """compute_mask.py's compute_mask and clips on stored spectra tgt, mix [T][F] complex64: mask
+        [T][F] float32 ([T][2F] for crm); numpy arrays, device tensors or device addresses.  Returns
+        (cells over the cutoff, cells below zero, their sum) or None."""
+        st = (TfmaskStats * 1)() if want_stats else None
+        self._run("setk_tf_mask", tfmask_kind(kind), _ptr(tgt), _ptr(mix), int(T), int(F), float(cutoff), _ptr(mask),
+                  ctypes.addressof(st) if want_stats else None, stream=stream)
+        return self._stats_out(st)[0] if want_stats else None
+
+    def tf_apply(self, spec, mask, T, F, out, phase_ref=None, stream=None):
+        """out = spec x mask, or |spec| x mask x exp(i angle(phase_ref)); [T][F] each."""
+        self._run("setk_tf_apply", _ptr(spec), _ptr(mask), _ptr(phase_ref), int(T), int(F), _ptr(out), stream=stream)
+
+    def tf_mask_batch(self, kind, tgt_ptrs, mix_ptrs, num_samples, mask_ptrs, cutoff=-1.0, status=None, flags=0,
+                      want_stats=True, stream=None):
+        """Pairs of device waveforms (int16 with FLAG_IN_PCM16) -> device masks float32 [T_u][257]
+        ([T_u][514] for crm) in one fused launch; status int32[n] or None.  Returns the statistics of
+        every utterance or None."""
+        n = len(mix_ptrs)
+        st = (TfmaskStats * n)() if want_stats else None
+        self._run("setk_tf_mask_batch", tfmask_kind(kind), n, _ptrs(tgt_ptrs, n), _ptrs(mix_ptrs), _ints(num_samples, n),
+                  float(cutoff), _ptrs(mask_ptrs, n), ctypes.addressof(st) if want_stats else None, _ptr(status),
+                  int(flags), stream=stream)
+        return self._stats_out(st) if want_stats else None
+
+    def tf_separate_batch(self, mix_ptrs, num_samples, mask_ptrs, wave_ptrs, phase_ptrs=None, norm=None, nsamps=None,
+                          status=None, flags=0, stream=None):
+        """Device mixtures and device masks [T_u][257] -> device waveforms: one fused forward launch,
+        one inverse launch, one scaling launch.  norm: per utterance, > 0 renorms to that max-abs;
+        nsamps: per utterance, >= 0 keeps that length."""
+        n = len(mix_ptrs)
+        norm = None if norm is None else np.ascontiguousarray(norm, dtype=np.float32)
+        self._run("setk_tf_separate_batch", n, _ptrs(mix_ptrs), _ptrs(phase_ptrs, n), _ints(num_samples, n),
+                  _ptrs(mask_ptrs, n), _ptr(norm), _ints(nsamps, n), _ptrs(wave_ptrs, n), _ptr(status), int(flags),
+                  stream=stream)
+
+    def oracle_separate_batch(self, kind, num_targets, mix_ptrs, target_ptrs, num_samples, wave_ptrs, nsamps=None,
+                              status=None, flags=0, stream=None):
+        """Device mixtures and num_targets device references each (target_ptrs[u * K + k]) -> device
+        waveforms wave_ptrs[u * K + k] = inverse_stft(mixture x mask_k)."""
+        n = len(mix_ptrs)
+        self._run("setk_oracle_separate_batch", tfmask_kind(kind), n, int(num_targets), _ptrs(mix_ptrs),
+                  _ptrs(target_ptrs), _ints(num_samples, n), _ints(nsamps, n), _ptrs(wave_ptrs), _ptr(status),
+                  int(flags), stream=stream)
 
     # -- SI-SNR scoring ---------------------------------------------------------------
     def si_snr_batch(self, num_src, est_ptrs, est_strides, ref_ptrs, ref_strides, num_samples, pair, best=None,

@@ -14,8 +14,8 @@ OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libsetk_hip.so")
 # The one list of translation units (`python setk_amd/build.py --units` prints it for the shell
 # recipes under tools/): the kernel units, then the C ABI front end by feature (capi.h).
-SOURCES = ["pass1.hip", "pass1_mc.hip", "pass2.hip", "pass2_mc.hip", "solve.hip", "modular.hip", "cgmm.hip", "cgmm_bin.hip", "cgmm_k.hip", "cacgmm.hip", "wpe.hip", "auxiva.hip", "ssl.hip", "spatial.hip", "ns.hip", "simu.hip", "online.hip", "wide.hip", "metric.hip", "rir.hip", "comm.hip", "hostio.hip",
-           "capi_support.hip", "capi_handle.hip", "capi_stft.hip", "capi_modular.hip", "capi_fused.hip", "capi_cgmm.hip", "capi_cacgmm.hip", "capi_wpe.hip", "capi_auxiva.hip", "capi_ssl.hip", "capi_spatial.hip", "capi_ns.hip", "capi_simu.hip", "capi_online.hip", "capi_metric.hip", "capi_rir.hip"]
+SOURCES = ["pass1.hip", "pass1_mc.hip", "pass2.hip", "pass2_mc.hip", "solve.hip", "modular.hip", "cgmm.hip", "cgmm_bin.hip", "cgmm_k.hip", "cacgmm.hip", "wpe.hip", "auxiva.hip", "ssl.hip", "spatial.hip", "ns.hip", "simu.hip", "online.hip", "wide.hip", "metric.hip", "rir.hip", "tfmask.hip", "comm.hip", "hostio.hip",
+           "capi_support.hip", "capi_handle.hip", "capi_stft.hip", "capi_modular.hip", "capi_fused.hip", "capi_cgmm.hip", "capi_cacgmm.hip", "capi_wpe.hip", "capi_auxiva.hip", "capi_ssl.hip", "capi_spatial.hip", "capi_ns.hip", "capi_simu.hip", "capi_online.hip", "capi_metric.hip", "capi_rir.hip", "capi_tfmask.hip"]
 HEADERS = ["common.h", "fft512.h", "dpp.h", "covar_fold.h", "mcdft.h", "mcdft_tables.h", "jacobi_herm.h", "capi.h", os.path.join("..", "..", "include", "setk_hip.h")]
 ARCH = "gfx950"
 
@@ -81,6 +81,7 @@ def unit_flags(src, arch=ARCH):
              "wide.hip": [],
              "metric.hip": [],
              "rir.hip": [],
+             "tfmask.hip": [],
              "comm.hip": []}   # (the capi_*.hip units hold no kernel)
     # solve.hip and modular.hip hold a kernel each that must round like numpy operation by operation
     # (lu_refusal_kernel's LAPACK-order elimination; the Kaldi compressed-matrix decode) behind

@@ -567,4 +567,49 @@ hipError_t launch_rir_images(const RirChan* d_chans, const RirItem* d_items, int
                              hipStream_t s);
 hipError_t launch_rir_finish(const RirChan* d_chans, int n_chans, hipStream_t s);
 
+// Oracle TF masks and mask-based separation (tfmask.hip): the cell arithmetic of compute_mask.py
+// and oracle_separate.py on stored spectra, and fused behind the 512-point forward transform.
+constexpr int kTfIbm = 0, kTfIrm = 1, kTfIam = 2, kTfPsm = 3, kTfPsa = 4, kTfCrm = 5;  // = SETK_TFMASK_*
+constexpr int kTfModeMask = 0, kTfModeSeparate = 1, kTfModeOracle = 2;
+constexpr int kTfMaxTargets = 8;      // = SETK_TFMASK_MAX_TARGETS
+constexpr int kTfChunk = 2048;        // cells per workgroup of the stored-spectra kernels (one slot each)
+struct TfStats {                      // = setk_tfmask_stats
+    long long over, below;
+    double below_sum;
+};
+struct TfFold {                       // one mask's statistics: the slots summed in their order by one owner
+    const unsigned long long* counts; // [2] over | below
+    const double* slots;
+    TfStats* out;
+    int nslots, pad_;
+};
+struct TfUtt {                        // one utterance of a forward launch
+    const void* mix;                  // float32 or int16 [num_samples]
+    const void* aux[kTfMaxTargets];   // mask: [0] the target; separation: [0] the phase reference or null;
+                                      // oracle: the K targets
+    void* out[kTfMaxTargets];         // mask: [0] float32 [T][F] ([T][2F] crm); separation: [0] complex64
+                                      // [T][F]; oracle: K times complex64 [T][F]
+    const float* mask;                // separation: [T][F]
+    int* status;                      // one word
+    unsigned long long* counts;       // mask: [2]
+    int num_samples, num_frames;
+};
+struct TfFwdArgs {
+    const TfUtt* utts;
+    const WorkItem* items;            // WorkItem::part: the item's slot
+    const float* window;              // [512], x 0.5 (PCM16: x 2^-16)
+    const float2* tw256;
+    const float2* tw512;
+    double* slots;                    // mask: one partial sum per item
+    StftGeom g;
+    float cutoff;
+    int num_targets;
+};
+hipError_t launch_tf_mask(int kind, const float* tgt, const float* mix, size_t cells, int F, float cutoff,
+                          float* mask, unsigned long long* counts, double* slots, int* status, hipStream_t s);
+hipError_t launch_tf_fold(const TfFold* d_jobs, int n, hipStream_t s);
+hipError_t launch_tf_apply(const float* spec, const float* mask, const float* phase_ref, size_t cells, float* out,
+                           hipStream_t s);
+hipError_t launch_tf_forward(int mode, int kind, bool pcm16, const TfFwdArgs& a, int n_items, hipStream_t s);
+
 }  // namespace setk

@@ -19,3 +19,4 @@ from .simu import BatchSimulator  # noqa: F401
 from .online import BatchOnlineEnhancer  # noqa: F401
 from .metric import BatchSiSnr  # noqa: F401
 from .rir import BatchRirGenerator  # noqa: F401
+from .tfmask import BatchMaskComputer, BatchMaskSeparator, BatchOracleSeparator  # noqa: F401
