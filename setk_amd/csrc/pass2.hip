@@ -377,8 +377,16 @@ hipError_t launch_pass2_online(int C, const Pass2Args& a, int n_items, hipStream
 
 // ---------------------------------------------------------------------------
 // renorm: samps * norm / (max|samps| + eps)   (libs/utils.py:166-168), float32
-// or PCM16 (libsndfile float->short: lrint(x * 32767)) output.
+// or PCM16 output.  The 16-bit branch quantises the float32 value the float branch would have
+// written, y = float32(src * sc), by the project's one float -> PCM_16 rule (wavio.float_to_pcm16,
+// float_to_pcm16_kernel): rint(y * 32767) with the product in double (exact there), no clipping --
+// a value out of range wraps.  So a 16-bit output equals the host writer's file of the float output,
+// sample for sample (tests/test_gpu_sample_conformance.py).
 // ---------------------------------------------------------------------------
+__device__ __forceinline__ short quantise_pcm16(float y) {
+    return (short)(long long)rint((double)y * 32767.0);
+}
+
 __global__ __launch_bounds__(256) void scale_kernel(ScaleArgs a) {
     const int u = blockIdx.y;
     const UttDesc ud = a.utts[u];
@@ -403,13 +411,10 @@ __global__ __launch_bounds__(256) void scale_kernel(ScaleArgs a) {
         short4* d4 = reinterpret_cast<short4*>(dst);
         for (int i = i0; i < n4; i += stride) {
             const float4 v = s4[i];
-            d4[i] = make_short4((short)(int)rintf(v.x * sc * 32767.f), (short)(int)rintf(v.y * sc * 32767.f),
-                                (short)(int)rintf(v.z * sc * 32767.f), (short)(int)rintf(v.w * sc * 32767.f));
+            d4[i] = make_short4(quantise_pcm16(v.x * sc), quantise_pcm16(v.y * sc), quantise_pcm16(v.z * sc),
+                                quantise_pcm16(v.w * sc));
         }
-        for (int i = 4 * n4 + i0; i < n; i += stride) {
-            const float v = rintf(src[i] * sc * 32767.f);
-            dst[i] = (int16_t)(int)v;
-        }
+        for (int i = 4 * n4 + i0; i < n; i += stride) dst[i] = quantise_pcm16(src[i] * sc);
     } else {
         float* dst = reinterpret_cast<float*>(ud.wave_out);
         if (sc == 1.f && dst == src) return;

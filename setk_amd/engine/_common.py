@@ -305,7 +305,8 @@ class _Engine(object):
 
     def _unfused_tail(self, enh, T, a, renorm=True):
         """The tail of the stand-alone operator paths: inverse transform of the T x F tensor `enh`,
-        renorm to max |a|, rounding when PCM16 goes out; returns the host waveform."""
+        renorm to max |a|, quantised by the writer's rule when PCM16 goes out (setk_float_to_pcm16:
+        rint(x * 32767) in float64, wrapping); returns the host waveform."""
         torch, ctx = self.torch, self.ctx
         L = ctx.istft_num_samples(T)
         wave = torch.empty((1, L), dtype=torch.float32, device=self.dev)
@@ -313,5 +314,7 @@ class _Engine(object):
         ctx.istft(enh.reshape(1, T, self.num_bins), 1, T, None, norm, wave)
         out = wave[0]
         if self.pcm16:
-            out = torch.round(out * 32767.0).to(torch.int16)
+            out = torch.empty(L, dtype=torch.int16, device=self.dev)
+            if L > 0:
+                ctx.float_to_pcm16(wave, 1, L, out)
         return out.cpu().numpy()

@@ -167,9 +167,9 @@ def test_engine_matches_model_and_is_reproducible(C):
     f = eng.run([p.astype(np.float32) / np.float32(32768.0) for p in pcm])
     for k, (i16, f32) in enumerate(zip(q, f)):
         assert i16.dtype == np.int16 and i16.shape == f32.shape
-        # (the renorm kernel quantises its float32 product, the writer's rule rounds in float64:
-        #  a sample on a rounding boundary may differ by one step)
-        assert np.max(np.abs(i16.astype(np.int32) - float_to_pcm16(f32).astype(np.int32))) <= 1, k
+        # (the renorm kernel quantises the float32 sample by the writer's rule, rint(x * 32767) in
+        #  float64: the 16-bit output is the writer's file of the float output, sample for sample)
+        assert np.array_equal(i16, float_to_pcm16(f32)), k
         ref = model_waves(pcm[k].astype(np.float32) / np.float32(32768.0), EPOCHS)
         for n in range(C):
             dev = pcm16_rel_rms(i16[n], ref[n])
